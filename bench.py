@@ -18,11 +18,19 @@ invocation (`speedup_vs_n1_ms`); `--scaling strong` makes the strong shape the h
 
 Prints ONE JSON line (rank 0).  Timing protocol: W warm-up steps, two steady steps for an estimate, then untimed "settling"
 steps until the chip has run STEADY-STATE steps for >= 1.5 s (DVFS settles over seconds), then EXACTLY K steps between barrier +
-synchronize pairs with no instrumentation inside, then `sustained` (200 more steps, outside `value`); the per-kernel HIP-event
-times and `launches_per_step` come from a SEPARATE eager pass after the timed one; `box_calibration_before` / `box_calibration`
-(N = 1) = ~1 s of vendor bf16 GEMMs before the warm-up steps and after all of that: a box-speed indicator (boxes of the pool differ
-by up to 10 % with unchanged code).  `roofline`
-prices the kernel with the largest share of the step, as a fraction of the dense bf16/fp16 MFMA peak both by the
+synchronize pairs with no instrumentation inside.  The trainer's state (parameters, Adam moments, step counters, draw counter) is
+put back after the settling steps to where the warm-up left it, so the K timed steps compute the same for the same arguments
+whatever number of settling steps the clock asked for.  A plain run stops there: `value`, `ms_per_step` and the workload.
+
+    --dump-outputs DIR   after the timed steps: what the LAST timed step returned (loss, per-ray rgb) and the parameters it left,
+                         as DIR/<name>.npy in float32 (a fixed, seeded sample of an array when all of them exceed 64 MB)
+    --full               everything else, after the timed steps: `sustained` (~10 s more steps, outside `value`); at N > 1 the
+                         `strong` sub-record; per-kernel HIP-event times and `launches_per_step` from a SEPARATE eager pass;
+                         `box_calibration_before` / `box_calibration` (N = 1) = ~1 s of vendor bf16 GEMMs before the warm-up
+                         steps and after all of that: a box-speed indicator (boxes of the pool differ by up to 10 % with
+                         unchanged code); `roofline`, `mlp_microbench`, `step_tflops*` and `cpu_baseline` (below).
+
+`roofline` prices the kernel with the largest share of the step, as a fraction of the dense bf16/fp16 MFMA peak both by the
 reference network's algorithmic FLOPs and by the FLOPs the build executes (the linear feats layer is folded into the
 heads); `traffic` / `mfma_busy` come from the committed rocprofv3 PMC pass of the SAME kernel sources
 (profiles/r05_pmc.json, keyed by a hash of csrc/; `traffic_live` false says so), null when the sources have changed since.  `cpu_baseline` times the
@@ -214,6 +222,56 @@ def pmc_record(config, dtype):
                       "HBM bytes = 2 x FETCH_SIZE + WRITE_SIZE per launch (gfx950 correction, MI355X_MICROARCH.md section HBM)"
 
 
+def trainer_snapshot(trainer):
+    """Everything a FusedTrainer step reads and advances: flat parameters, Adam moments, the device step state (draw counter, Adam
+    step counts and beta powers, loss ring) and the host's mirrors of those counters.  Returns restore(), which copies it back in
+    place (the captured graphs keep their addresses)."""
+    dev = [trainer.flat_param, trainer.exp_avg, trainer.exp_avg_sq, trainer.state]
+    saved = [t.clone() for t in dev]
+    host = (trainer._rng_step, dict(trainer.adam_steps), list(trainer._state_adam))
+
+    def restore():
+        for dst, src in zip(dev, saved):
+            dst.copy_(src)
+        trainer._rng_step, trainer.adam_steps, trainer._state_adam = host[0], dict(host[1]), list(host[2])
+    return restore
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> host float32 array.  Written as out_dir/<name>.npy; when they exceed DUMP_BUDGET_BYTES together, every
+    array above its share is replaced by a fixed, seeded sample of its flattened elements (same indices on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    scale = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        keep = int(a.size * scale)
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def headline(a, world, rays_gpu, base_cfg, backend, settle, dt, loss, dropped):
+    """The result line of every run: the timed steps and the workload they ran."""
+    rays_step = world * rays_gpu
+    return {
+        "metric": METRIC, "value": rays_step * a.steps / dt, "unit": "rays/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None,
+        "dtype": a.dtype, "data": "synthetic",
+        "config": {"workload": f"BASELINE config {base_cfg}: Djibouti-shaped synthetic rays, spsbrdf-nerf {a.config} train step "
+                               f"(pass1 {a.samples} + guided {a.guided} samples/ray, F=512, 8 Siren layers, PE10, ds_lambda=10), "
+                               f"{rays_gpu} rays/GPU/step ({rays_step} rays per global step, {a.scaling} scaling)",
+                   "rays_per_gpu": rays_gpu, "n_samples": a.samples, "guided_samples": a.guided, "parallelism": f"dp{world}",
+                   "backend": (backend if world > 1 else None), "settle_steps": settle},
+        "final_loss": float(loss), "dropped_nonfinite_grad_elems": list(dropped), "full": bool(a.full),
+    }
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -233,7 +291,10 @@ def parse_args():
                                                                   "--sustained-seconds take)")
     ap.add_argument("--sustained-seconds", type=float, default=10.0, help="length of the `sustained` run when --sustained-steps is 0 "
                                                                           "(0: none); long enough for an external GPU-busy sampler")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out `cpu_baseline`")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: sustained run, strong "
+                                                        "scaling (N > 1), per-kernel times, roofline, box calibration, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -352,24 +413,41 @@ def main():
         barrier()
         return agree_max(time.perf_counter() - t0), out
 
-    def settle_then_time(fn, warmup, steps):
+    def settle_then_time(fn, tr, warmup, steps):
         """W warm-up steps (lazy initialisation, allocator, graph capture), then the per-step time from two STEADY-STATE steps,
         then settling steps until the chip has run >= settle_seconds of steady-state steps (its clock settles over seconds),
-        then exactly `steps` timed steps."""
+        then the trainer `tr` back to its state after the warm-up, then exactly `steps` timed steps."""
         barrier()
         for i in range(warmup):
             fn(i)
+        restore = trainer_snapshot(tr)
         est, _ = timed(fn, 2)
         est /= 2
         n_settle = min(int(math.ceil(a.settle_seconds / max(est, 1e-5))), 20000) if a.settle_seconds > 0 else 0
         for i in range(n_settle):
             fn(i)
+        restore()
         dt_, out = timed(fn, steps)
         return dt_, out, n_settle
 
     # box-speed indicator BEFORE anything is timed (and again after everything, below): both are printed (VERDICT r4 item 6)
-    calib_before = box_calibration(dev, when="before the warm-up steps") if world == 1 else None
-    dt, (loss, _), settle = settle_then_time(run, a.warmup, a.steps)
+    calib_before = box_calibration(dev, when="before the warm-up steps") if world == 1 and a.full else None
+    dt, (loss, rgb), settle = settle_then_time(run, trainer, a.warmup, a.steps)
+    # what the last timed step computed, copied before anything else runs (a graph replay overwrites its outputs in place)
+    if a.dump_outputs and rank == 0:
+        outputs = {"loss": loss.float().reshape(1).cpu().numpy(), "rgb": rgb.float().cpu().numpy()}
+        outputs.update({"param." + n: p.detach().float().cpu().numpy() for n, p in model.named_parameters()})
+        dump_outputs(a.dump_outputs, outputs)
+    if not a.full:
+        dropped = trainer.dropped_grad_elems()
+        if rank == 0:
+            line = headline(a, world, rays_gpu, base_cfg, backend, settle, dt, loss, dropped)
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(line) + "\n").encode())
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- sustained: a longer run after the timed region, outside `value` (does the step hold its time?)
     sustained = None
     n_sus = a.sustained_steps if a.sustained_steps > 0 else int(math.ceil(a.sustained_seconds / max(dt / a.steps, 1e-5)))
@@ -390,13 +468,13 @@ def main():
         bs = [{k: v[lo:hi].contiguous() for k, v in synthetic_batch(a.rays, i + 1, dev).items()} for i in range(4)]
         run_s = lambda i: tr_s.step(bs[i % 4]["rays"], bs[i % 4]["rgbs"], valid_depth=bs[i % 4]["valid_depth"], depths=bs[i % 4]["depths"],
                                     depth_std=bs[i % 4]["depth_std"], near_far=(0.0, 2.0), **flags)
-        dt_s, _, _ = settle_then_time(run_s, a.warmup, a.steps)
+        dt_s, _, _ = settle_then_time(run_s, tr_s, a.warmup, a.steps)
         torch.manual_seed(0)
         tr_1 = FusedTrainer(load_model(args).to(dev), args, lr=args.lr, ds_lambda=args.ds_lambda, strict_rng=False, data_parallel=False)
         b1 = [synthetic_batch(a.rays, i + 1, dev) for i in range(4)]
         run_1 = lambda i: tr_1.step(b1[i % 4]["rays"], b1[i % 4]["rgbs"], valid_depth=b1[i % 4]["valid_depth"], depths=b1[i % 4]["depths"],
                                     depth_std=b1[i % 4]["depth_std"], near_far=(0.0, 2.0), **flags)
-        dt_1, _, _ = settle_then_time(run_1, a.warmup, a.steps)
+        dt_1, _, _ = settle_then_time(run_1, tr_1, a.warmup, a.steps)
         strong = {"rays_per_global_step": a.rays, "rays_per_gpu": hi - lo, "ms_per_step": dt_s / a.steps * 1e3,
                   "value": a.rays * a.steps / dt_s, "unit": "rays/s",
                   "n1_shape_ms_per_step": dt_1 / a.steps * 1e3, "speedup_vs_n1_ms": dt_1 / dt_s,
@@ -470,15 +548,8 @@ def main():
     # [+ the analytic-normal adjoint]): 2.002 GFLOP (Lambertian), 3.761 GFLOP (RPV111 + analytic normals, fused accounting)
     per_ray_ref = a.samples * fpp[False]["field_fwd_sigma"] + (a.samples + a.guided) * 3 * (
         fpp[False]["field_fwd_full"] + fpp[False].get("field_adjoint", 0))
-    line = {
-        "metric": METRIC, "value": rays_step * a.steps / dt, "unit": "rays/s", "n_gpus": world, "steps": a.steps,
-        "warmup": a.warmup, "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None,
-        "dtype": a.dtype, "data": "synthetic",
-        "config": {"workload": f"BASELINE config {base_cfg}: Djibouti-shaped synthetic rays, spsbrdf-nerf {a.config} train step "
-                               f"(pass1 {a.samples} + guided {a.guided} samples/ray, F=512, 8 Siren layers, PE10, ds_lambda=10), "
-                               f"{rays_gpu} rays/GPU/step ({rays_step} rays per global step, {a.scaling} scaling)",
-                   "rays_per_gpu": rays_gpu, "n_samples": a.samples, "guided_samples": a.guided, "parallelism": f"dp{world}",
-                   "backend": (backend if world > 1 else None), "settle_steps": settle},
+    line = headline(a, world, rays_gpu, base_cfg, backend, settle, dt, loss, dropped)
+    line.update({
         "roofline": {"bound": "mfma", "kernel": dom, "achieved": mfma[dom]["tflops"], "peak": peak, "unit": "TFLOP/s",
                      "frac": mfma[dom]["tflops"] / peak, "frac_algorithmic": mfma[dom]["tflops"] / peak,
                      # the OTHER accounting, never to be confused with the kernel fraction: rays/s x SURVEY section 8(d)'s FLOP per
@@ -508,10 +579,9 @@ def main():
         "step_tflops": flops_step[False] / step_s / 1e12, "step_frac_of_peak": flops_step[False] / step_s / 1e12 / peak,
         "step_tflops_executed": flops_step[True] / step_s / 1e12, "step_frac_of_peak_executed": flops_step[True] / step_s / 1e12 / peak,
         "step_tflops_reference_accounting": flops_ref / step_s / 1e12,
-        "kernels": kernels, "final_loss": float(loss), "dropped_nonfinite_grad_elems": list(dropped),
-        "sustained": sustained, "strong": strong,
+        "kernels": kernels, "sustained": sustained, "strong": strong,
         "launches_per_step": sum(k["launches_per_step"] for k in kernels.values()),
-    }
+    })
     if world == 1:
         line["box_calibration"] = box_calibration(dev, when="after everything that is timed")
         line["box_calibration_before"] = calib_before

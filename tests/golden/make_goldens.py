@@ -600,9 +600,132 @@ def gen_init(ref):
     save("init_state_dicts", seed=7, **out)
 
 
+# ------------------------------------------------------------------------------ random configurations
+# tests/test_oracle_vs_reference.py: the oracle against the reference on a family of RANDOM configurations.  Each case
+# stores its configuration, its inputs and the reference's outputs (and draws), so the test needs nothing but the fixture.
+RANDOM_FIELD_SEEDS = range(16)
+RANDOM_RENDER_SEEDS = range(12)
+RANDOM_CASES_PER_FILE = 4
+
+
+def random_config(rng):
+    family = rng.choice(["lambert", "rpv", "hapke", "microfacet"])
+    kw = dict(feat=int(rng.choice([32, 64])), layers=int(rng.integers(2, 9)), siren=bool(rng.random() < 0.7), mapping=bool(rng.random() < 0.8),
+              normal=str(rng.choice(["none", "learned", "analystic", "analystic_learned"])),
+              input_viewdir=int(rng.random() < 0.35), beta=bool(rng.random() < 0.35), n_samples=int(rng.choice([8, 16])),
+              guided_samples=int(rng.choice([8, 16])))
+    if family == "rpv":
+        kw.update(funcM=int(rng.random() < 0.7), funcF=int(rng.random() < 0.7), funcH=int(rng.random() < 0.7), dim_RPV=int(rng.choice([1, 3])))
+        if not (kw["funcM"] or kw["funcF"] or kw["funcH"]):
+            kw["funcM"] = 1
+    elif family == "hapke":
+        kw.update(b=1, c=int(rng.random() < 0.7), theta=int(rng.random() < 0.5))
+    elif family == "microfacet":
+        kw.update(roughness=True)
+    if family != "lambert" and kw["normal"] == "none":
+        kw["normal"] = "learned"
+    return FieldConfig(**kw)
+
+
+def _cfg_json(cfg):
+    import dataclasses
+    import json
+    return np.array(json.dumps(dataclasses.asdict(cfg)))
+
+
+def random_field_case(ref, seed):
+    """Field forward + every parameter gradient of the reference on random configuration `seed`."""
+    import json
+    rng = np.random.default_rng(31000 + seed)
+    cfg = random_config(rng)
+    pseed = 20 + seed
+    model, csum = build_ref_model(ref, cfg, seed=pseed)
+    B = int(rng.integers(1, 120))
+    g = torch.Generator().manual_seed(seed)
+    xyz = torch.rand(B, 3, generator=g) * 2 - 1
+    dirs = torch.nn.functional.normalize(torch.randn(B, 3, generator=g), dim=-1)
+    t_in = torch.randn(B, cfg.t_dim, generator=g)
+    flags = dict(apply_brdf=bool(rng.random() < 0.8), apply_theta=bool(rng.random() < 0.7),
+                 nr_an_on=cfg.normal in ("analystic", "analystic_learned"), nr_lr_on=cfg.normal in ("learned", "analystic_learned"))
+    t_ref = t_in.clone().requires_grad_(True)
+    out_ref = quiet(model, xyz.clone(), input_dir=dirs, input_t=t_ref if cfg.beta else None, **flags)
+    coef = torch.randn(out_ref.shape, generator=g)
+    (out_ref * coef).sum().backward()
+    case = dict(cfg=_cfg_json(cfg), flags=np.array(json.dumps(flags)), param_seed=pseed, param_checksum=csum, xyz=xyz, dirs=dirs,
+                t_in=t_in, coef=coef, out=out_ref)
+    if cfg.beta:
+        case["t_grad"] = t_ref.grad
+    for k, v in model.named_parameters():
+        if v.grad is not None:                   # absent: the reference leaves this parameter without a gradient
+            case["grad/" + k] = v.grad
+    return case
+
+
+def random_render_case(ref, seed):
+    """render_rays of the reference on random configuration `seed`, its random draws recorded in call order."""
+    import json
+    rng = np.random.default_rng(33000 + seed)
+    cfg = random_config(rng)
+    kw = dict(vars(cfg))
+    brdf = bool(cfg.roughness or cfg.RPV or cfg.b)
+    gsam_only = bool(rng.random() < 0.3)
+    if brdf and gsam_only and rng.random() < 0.5:
+        kw["sun_v"] = "analystic"
+    if cfg.RPV and rng.random() < 0.3:
+        kw["MultiBRDF"] = True
+    kw["noise_std"] = float(rng.choice([0.0, 0.3]))
+    cfg = FieldConfig(**kw)
+    R = int(rng.integers(2, 40))
+    mode = "train" if rng.random() < 0.5 else "test"
+    flags = dict(apply_brdf=brdf and bool(rng.random() < 0.85), apply_theta=bool(rng.random() < 0.7), cos_irra_on=bool(rng.random() < 0.6),
+                 gsam_only=gsam_only)
+    if cfg.sun_v == "analystic":
+        flags["apply_brdf"] = True
+    pseed = 30 + seed
+    model, csum = build_ref_model(ref, cfg, seed=pseed)
+    rays = sat_rays(R, 40 + seed)
+    g = torch.Generator().manual_seed(seed)
+    dk = {}
+    if mode == "train" and rng.random() < 0.6:
+        dk = dict(valid_depth=(torch.rand(R, generator=g) < 0.6).float(),
+                  target_depths=torch.stack([0.8 + 0.4 * torch.rand(R, generator=g), torch.rand(R, generator=g)], -1),
+                  target_std=0.02 + 0.05 * torch.rand(R, generator=g))
+    models = {"coarse": model}
+    case = dict(cfg=_cfg_json(cfg), flags=np.array(json.dumps(flags)), mode=np.array(mode), param_seed=pseed, param_checksum=csum,
+                rays=rays,
+                **{"dk/" + k: v for k, v in dk.items()})
+    ts = None
+    if cfg.beta:
+        torch.manual_seed(50 + seed)
+        emb = torch.nn.Embedding(5, cfg.t_dim)
+        ts = torch.randint(0, 5, (R,), generator=g)
+        models["t"] = emb
+        case.update(ts=ts, emb=emb.weight.detach())
+    with RecordRandoms(torch.Generator().manual_seed(2)) as rec, torch.no_grad():
+        res, bt = quiet(ref["rendering"].render_rays, models, ref_args(cfg), rays, ts, mode=mode, **flags, **dk)
+    case.update(brdf_type=np.array(json.dumps(bt)), res_keys=np.array("\n".join(res)),
+                **{f"rand{i}": t for i, t in enumerate(rec.log)},
+                **{"res/" + k: (v if torch.is_tensor(v) else torch.as_tensor(v)) for k, v in res.items()})
+    return case
+
+
+def gen_random_configs(ref):
+    for kind, seeds, make in (("field", RANDOM_FIELD_SEEDS, random_field_case), ("render", RANDOM_RENDER_SEEDS, random_render_case)):
+        seeds = list(seeds)
+        for lo in range(0, len(seeds), RANDOM_CASES_PER_FILE):
+            chunk = seeds[lo:lo + RANDOM_CASES_PER_FILE]
+            arrays = {}
+            for s in chunk:
+                arrays.update({f"s{s}/{k}": v for k, v in make(ref, s).items()})
+            save(f"random_{kind}_{chunk[0]:02d}_{chunk[-1]:02d}", **arrays)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(4)
     ref = import_reference()
+    if "--only-random-configs" in sys.argv:
+        gen_random_configs(ref)
+        sys.exit(0)
     if "--only-init" in sys.argv:
         gen_init(ref)
         sys.exit(0)
@@ -639,3 +762,4 @@ if __name__ == "__main__":
     gen_viewdir(ref)
     gen_beta(ref)
     gen_branches(ref)
+    gen_random_configs(ref)
