@@ -14,8 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbrdfnerf_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-         "-Wno-pass-failed", "-Wno-unused-result"]
+FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wno-pass-failed", "-Wno-unused-result"]
 
 
 def sources():
@@ -68,11 +67,22 @@ FILE_FLAGS = {"field_wgrad.hip": ("-mllvm", "-amdgpu-sched-strategy=max-ilp"),
               "field_bwd.hip": _TRACKERS, "field_adjoint.hip": _TRACKERS, "field_adjbwd.hip": _TRACKERS}
 
 
+def compile_command(src, out, defines=(), extra_flags=(), file_flags=None, asm=False):
+    """The hipcc command line of one source file: FLAGS, the include directories of the tree `src` lies in, the file's FILE_FLAGS
+    (or its entry in `file_flags`), `extra_flags`, a -D per entry of `defines` ("NAME" or "NAME=value").  asm=True: the device
+    assembly (text) instead of an object.  build() and the profiles/ tools that compile a file on their own all go through here."""
+    csrc = os.path.dirname(os.path.abspath(src))
+    per_file = dict(FILE_FLAGS, **(file_flags or {}))
+    return [HIPCC] + FLAGS + ["-I" + os.path.join(os.path.dirname(os.path.dirname(csrc)), "include"), "-I" + csrc] + \
+        list(per_file.get(os.path.basename(src), ())) + list(extra_flags) + ["-D" + d for d in defines] + \
+        ["-x", "hip"] + (["--cuda-device-only", "-S"] if asm else ["-c"]) + [src, "-o", out]
+
+
 def build(verbose=False, force=False, defines=(), out=None, extra_flags=(), tag=None, file_flags=None):
     """defines/out/extra_flags/tag: build a VARIANT library (A/B experiments, profiles/): objects go to build/<tag>/, the result
-    to `out`; load it with BRDFNERF_HIP_LIB=<out>.  extra_flags: hipcc flags for every file (e.g. -mllvm options)."""
+    to `out`; load it with BRDFNERF_HIP_LIB=<out>.  extra_flags: hipcc flags for every file (e.g. -mllvm options).  file_flags: A/B
+    override of one file's extra flags ({basename: (flags...)})."""
     variant = bool(defines) or out is not None or bool(extra_flags) or bool(file_flags)
-    per_file = dict(FILE_FLAGS, **(file_flags or {}))     # file_flags: A/B override of one file's extra flags ({basename: (flags...)})
     if not variant and not force and not needs_build():
         return LIB
     tag = tag or "_".join(d.replace("=", "-") for d in defines) or "default"
@@ -89,8 +99,7 @@ def build(verbose=False, force=False, defines=(), out=None, extra_flags=(), tag=
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         stamp = os.path.basename(src) == "error.cpp"            # carries the source hash (so it is recompiled whenever any source changed)
-        cmd = [HIPCC] + FLAGS + list(per_file.get(os.path.basename(src), ())) + list(extra_flags) + ["-D" + d for d in defines] + \
-            (['-DBN_SOURCE_HASH="%s"' % sh] if stamp else []) + ["-x", "hip", "-c", src, "-o", obj]
+        cmd = compile_command(src, obj, list(defines) + (['BN_SOURCE_HASH="%s"' % sh] if stamp else []), extra_flags, file_flags)
         # an object is reused when it was compiled from these bytes with this command line (content key, not mtimes)
         key = hashlib.sha256(open(src, "rb").read() + hdr_bytes + " ".join(cmd).encode()).hexdigest()
         keys.append((obj + ".key", key))

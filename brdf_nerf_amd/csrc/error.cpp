@@ -2,12 +2,14 @@
 #include <atomic>
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
+#include <string>
 #include <hip/hip_runtime.h>
 #include <map>
 #include <mutex>
 #include <utility>
 #include "brdfnerf_hip.h"
-#include "diag.h"
+// (never common.h or a plain diag.h here: the defaults of the valued switches would make each of them look set to bn_build_flags())
 
 static thread_local char g_err[512] = "";
 
@@ -28,8 +30,20 @@ extern "C" int bn_abi_version(void) { return BN_ABI_VERSION; }
 #endif
 extern "C" const char *bn_source_hash(void) { return "BN_SOURCE_HASH=" BN_SOURCE_HASH + 15; }
 
-// Every -D switch a source file of the library reacts to is declared in diag.h (variant builds pass the same defines to every file).
-extern "C" const char *bn_build_flags(void) { return BN_BUILD_FLAGS_STRING; }
+// The switches of diag.h's list that were set on the command line, each followed by one space (variant builds pass the same
+// defines to every file).  A macro that is not defined stringifies, after expansion, to its own name; one that is set, to its value.
+#define BN_STR_(x) #x
+#define BN_STR(x) BN_STR_(x)
+extern "C" const char *bn_build_flags(void) {
+  static const std::string flags = [] {
+    std::string s;
+#define BN_SWITCH(NAME) if (strcmp(#NAME, BN_STR(NAME)) != 0) s += #NAME " ";
+#include "diag.h"
+#undef BN_SWITCH
+    return s;
+  }();
+  return flags.c_str();
+}
 
 static std::atomic<int> g_deterministic{0};
 int bn_deterministic() { return g_deterministic.load(std::memory_order_relaxed); }

@@ -4,16 +4,9 @@
 #include "common.h"
 
 #define BN_MAX_PASS 3
-#ifndef BN_DPH                    // (diag.h: an A/B build may pin 12 = the four-head layout of ABI <= 2, profiles/history/r02_ablation.txt)
 #define BN_DPH (3 * BN_MAX_HEADS)   // pre-activation gradients of the heads' (<= 3) outputs kept per point
-#endif
-// 32-column tiles per wave in a single-head pass (N = F/2 columns): NT/2 spreads the pass over all eight waves; NT keeps
-// half of them idle but halves the LDS fragment reads per MFMA (BN_HEAD_WIDE, A/B switch).
-#ifdef BN_HEAD_WIDE
-#define BN_SINGLE_HEAD_NTW(NT) (NT)
-#else
+// 32-column tiles per wave in a single-head pass (N = F/2 columns): NT/2 spreads the pass over all eight waves.
 #define BN_SINGLE_HEAD_NTW(NT) ((NT) > 1 ? (NT) / 2 : 1)
-#endif
 
 struct FieldGeom {
   int F, L, skip, pe_freqs, act;

@@ -453,35 +453,24 @@ __global__ __launch_bounds__(WAVES * 64, 2) void field_bwd_kernel(const BwdArgs 
     zero_acc<MT, NT>(acc);
     T *zdst = (T *)(A.stash + A.sl.dZ[l]) + (size_t)m0 * F;
     if (!NATZ && !ride) tile_to_global<T>(ACT, LDA, zdst, F, BM, F);
-    // (BN_BWD_D_AT, diag.h: where the barrier-free trunk issues a layer's derivative loads: 0 before the GEMM, 1 between its halves, 2 behind it)
+    // (BN_BWD_D_AT, diag.h: where the barrier-free trunk issues a layer's derivative loads: 0 before the GEMM, 1 between its halves,
+    // 2 behind it - backward chain +4-5 % with 1 or 2, profiles/r04_ab_bwd_pingpong_tune.txt)
     if (wave_on) {
       if (!PING || BN_BWD_D_AT == 0) load_D(lo, 0, NPRE);
       const size_t off = A.pl.bwd_trunk[l] + (size_t)(ncol0 / 32) * KSF * 512;
       if constexpr (PING) {
-        const int half = KSF / 2;
-        NoSide none;
         pp_wait(WR + 0, 4 * it, &g_bwd_fault);                        // half 0 of dZ_l is written
         if (grp == 1) pp_wait(RD + 0, 4 * (it + 1), &g_bwd_fault);    // group 0 is done with its phase 1 of this layer: the lag
         BN_PH(12)
         __builtin_amdgcn_s_setprio(1);
-#ifdef BN_PP_SPLIT      // A/B switch (results unchanged): two half-GEMMs, each with its own weight prologue (round 4)
-        gemm_range<T, MT, NT, DP | BN_PP_NKS>(acc, packed + off, KSF, 0, half, ACT, LDA, lane, none);
-        BN_PH(9)
-        pp_signal(RD + 0 + grp, lane);
-        pp_wait(WR + 1, 4 * it, &g_bwd_fault);                        // half 1
-        BN_PH(12)
-        if (BN_BWD_D_AT == 1) load_D(lo, 0, NPRE);
-        gemm_range<T, MT, NT, DP | BN_PP_NKS>(acc, packed + off, KSF, half, half, ACT, LDA, lane, none);
-#else
+        // one weight stream over both column halves, as in the forward trunk (profiles/r05_ablation.txt item 1)
         if constexpr (sizeof(T) == 2) {        // (PING implies a 16-bit mode)
-          (void)half; (void)none;
-          gemm_trunk<T, MT, NT, (DP & (BN_GEMM_AFFINE - 1)), 32, 16>(acc, packed + off, KSF, ACT, LDA, lane, [&]() {
+          gemm_fixed<T, MT, NT, (DP & (BN_GEMM_AFFINE - 1)), 32, 16>(acc, packed + off, KSF, 0, ACT, LDA, lane, [&]() {
             pp_signal(RD + 0 + grp, lane);
             pp_wait(WR + 1, 4 * it, &g_bwd_fault);                    // half 1
             if (BN_BWD_D_AT == 1) load_D(lo, 0, NPRE);
           });
         }
-#endif
         __builtin_amdgcn_s_setprio(0);
         pp_signal(RD + 2 + grp, lane);
         if (BN_BWD_D_AT == 2) load_D(lo, 0, NPRE);

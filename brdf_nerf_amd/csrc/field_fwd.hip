@@ -97,11 +97,8 @@ __device__ __forceinline__ void fill_dir_row(const FwdArgs &A, int64_t gm, T *ro
 // free by now) ahead of the GEMM: the epilogue then reads them without queueing behind its own stash stores.
 // The hidden activations G are stashed in accumulator order like DG (one coalesced 16-byte store per lane).
 template <typename T, int MT, int NTW, int WAVES, bool KEEP, bool DIR, bool HOT, bool D16>
-__device__ __forceinline__ void head_pass(const FwdArgs &A, int p, const T *ACT, float *PRM, float *RED, int64_t m0, int64_t tile
-#ifdef BN_PHASE_TIMING
-                                          , unsigned long long (&ph_)[BN_PH_N], unsigned long long &pt_
-#endif
-) {
+__device__ __forceinline__ void head_pass(const FwdArgs &A, int p, const T *ACT, float *PRM, float *RED, int64_t m0, int64_t tile,
+                                          const BnPhaseClock &phc_) {
   constexpr int BM = MT * 32;
   constexpr bool FAST = Elem<T>::kFastMath;
   constexpr int DP = FwdDepth<T, KEEP>::value;
@@ -236,11 +233,6 @@ __device__ __forceinline__ void head_pass(const FwdArgs &A, int p, const T *ACT,
   BN_PH(11)
 }
 
-#ifdef BN_PHASE_TIMING
-#define BN_PH_ARGS , ph_, pt_
-#else
-#define BN_PH_ARGS
-#endif
 template <typename T, int MT, int NT, int WAVES, bool KEEP, bool DIR, bool D16>
 __global__ __launch_bounds__(WAVES * 64, 2) void field_fwd_kernel(const FwdArgs A) {
   typedef typename Elem<T>::vec4 vec4;
@@ -338,10 +330,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void field_fwd_kernel(const FwdArgs 
   int *WR = (int *)RED, *RD = WR + 2;   // RD[2 * h + g]
   const int grp = wave >> 2;
   BN_TL_DECL((char *)RED + 64 + 4096)
-  // (BN_GEMM_PRIO, diag.h: priority of a wave while it multiplies; 0 = none, as in rounds 1-3)
-#ifdef BN_PRIO_YOUNG      // A/B switch: static priority for the later-dispatched half (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-#endif
+  // (BN_GEMM_PRIO, diag.h: priority of a wave while it multiplies; 0 = none, as in rounds 1-3.  A static priority for the
+  // later-dispatched half of the waves instead measured unchanged: profiles/r05_ab_prio_wringlate_lambert.txt)
   // Anti-phase trunk: a wave's biases (its 64 columns) wait in LDS, [2][64] floats per wave behind the counters, and START the
   // accumulators - the epilogue has no bias add and no bias registers; layer l + 1's are fetched (one dword per lane) at the
   // top of layer l, ahead of every load and store of that layer, and parked after its GEMM.
@@ -375,34 +365,22 @@ __global__ __launch_bounds__(WAVES * 64, 2) void field_fwd_kernel(const FwdArgs 
       if (l == 0 || l == g.skip) gemm_seg<T, MT, NT, DP>(acc, w_pe, KSP, PE, LDP, lane);
       if (l > 0) {
         if (PING) {
-          const int half = KSF / 2;
-          NoSide none;
           BN_PH(1)
           pp_wait(WR + 0, 4 * l, &g_fwd_fault);                       // half 0 of Y_{l-1} is written
           if (grp == 1) pp_wait(RD + 0, 4 * l, &g_fwd_fault);         // group 0 is done with its phase 1 of this layer: the lag
           BN_PH(12)
           BN_TL(1)
           __builtin_amdgcn_s_setprio(BN_GEMM_PRIO);
-#ifdef BN_PP_SPLIT      // A/B switch (results unchanged): two half-GEMMs, each with its own weight prologue (rounds 1-4)
-          gemm_range<T, MT, NT, DP | BN_PP_NKS>(acc, w_h, KSF, 0, half, ACT, LDA, lane, none);
-          BN_PH(1)
-          BN_TL(2)
-          pp_signal(RD + 0 + grp, lane);
-          pp_wait(WR + 1, 4 * l, &g_fwd_fault);                       // half 1
-          BN_PH(13)
-          BN_TL(3)
-          gemm_range<T, MT, NT, DP | BN_PP_NKS>(acc, w_h, KSF, half, half, ACT, LDA, lane, none);
-#else
+          // one weight stream over both column halves, the hand-over behind k-step 16 (two half-GEMMs with a weight prologue
+          // each, rounds 1-4: profiles/r05_ablation.txt item 1, profiles/r05_ab_trunk_stream_lambert.txt)
           if constexpr (sizeof(T) == 2) {      // (PING implies a 16-bit mode; the fp32 instantiation never gets here)
-            (void)half; (void)none;
-            gemm_trunk<T, MT, NT, (DP & (BN_GEMM_AFFINE - 1)), 32, 16>(acc, w_h, KSF, ACT, LDA, lane, [&]() {
+            gemm_fixed<T, MT, NT, (DP & (BN_GEMM_AFFINE - 1)), 32, 16>(acc, w_h, KSF, 0, ACT, LDA, lane, [&]() {
               BN_TL(2)
               pp_signal(RD + 0 + grp, lane);
               pp_wait(WR + 1, 4 * l, &g_fwd_fault);                   // half 1
               BN_TL(3)
             });
           }
-#endif
           __builtin_amdgcn_s_setprio(0);
           BN_TL(4)
           pp_signal(RD + 2 + grp, lane);
@@ -552,15 +530,11 @@ __global__ __launch_bounds__(WAVES * 64, 2) void field_fwd_kernel(const FwdArgs 
     zero_acc<MT, 1>(sacc);
     zero_acc<MT, 1>(nacc);
     if (kon) {
-      NoSide none;
-#if !defined(BN_NO_FIXED_FULL) && !defined(BN_NO_FIXED_SIGMA)
       if constexpr (NT == 2 && WAVES == 8) {       // F = 512: four k-steps per wave, straight-line
-        (void)none; (void)nks;
         gemm_fixed<T, MT, 1, 4, 4, 0>(sacc, packed + A.pl.fwd_sigma, KSF, ks0, ACT, LDA, lane, NoMid());
         if (nlr) gemm_fixed<T, MT, 1, 4, 4, 0>(nacc, packed + A.pl.fwd_nlr, KSF, ks0, ACT, LDA, lane, NoMid());
-      } else
-#endif
-      {
+      } else {
+        NoSide none;
         gemm_range<T, MT, 1, DP>(sacc, packed + A.pl.fwd_sigma, KSF, ks0, nks, ACT, LDA, lane, none);
         if (nlr) gemm_range<T, MT, 1, DP>(nacc, packed + A.pl.fwd_nlr, KSF, ks0, nks, ACT, LDA, lane, none);
       }
@@ -695,8 +669,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void field_fwd_kernel(const FwdArgs 
 
   // ---------------------------------------------------------------- two-layer sigmoid heads, up to 2 per pass
   for (int p = 0; p < g.n_pass; ++p) {
-    if (g.pass_heads[p] == 2) head_pass<T, MT, NT, WAVES, KEEP, DIR, NT == 2, D16>(A, p, ACT, (float *)PE, RED, m0, tile BN_PH_ARGS);
-    else head_pass<T, MT, BN_SINGLE_HEAD_NTW(NT), WAVES, KEEP, DIR, NT == 2, D16>(A, p, ACT, (float *)PE, RED, m0, tile BN_PH_ARGS);
+    if (g.pass_heads[p] == 2) head_pass<T, MT, NT, WAVES, KEEP, DIR, NT == 2, D16>(A, p, ACT, (float *)PE, RED, m0, tile, phc_);
+    else head_pass<T, MT, BN_SINGLE_HEAD_NTW(NT), WAVES, KEEP, DIR, NT == 2, D16>(A, p, ACT, (float *)PE, RED, m0, tile, phc_);
   }
   BN_PH_FLUSH
   BN_CLK_END

@@ -12,79 +12,7 @@
 //     (n = 8g + 4h + e), so activations are written back to ACT[m][n..n+3] with one 8-byte store.
 #pragma once
 #include "field.h"
-
-// Phase-cycle instrumentation, compiled only into the diagnostic library built by profiles/phase_timing.py
-// (-DBN_PHASE_TIMING): per-wave shader-clock cycles spent between BN_PH() marks, summed over the grid.
-#ifdef BN_PHASE_TIMING
-#define BN_PH_N 16
-static __device__ unsigned long long bn_phase_clk[BN_PH_N + 1];
-#define BN_PH_DEFINE_READER(NAME)                                                                              \
-  extern "C" int NAME(unsigned long long *out, int reset) {                                                    \
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(bn_phase_clk), sizeof(unsigned long long) * (BN_PH_N + 1)) != hipSuccess) return -1; \
-    if (reset) {                                                                                               \
-      unsigned long long z[BN_PH_N + 1] = {0};                                                                 \
-      if (hipMemcpyToSymbol(HIP_SYMBOL(bn_phase_clk), z, sizeof(z)) != hipSuccess) return -1;                  \
-    }                                                                                                          \
-    return 0;                                                                                                  \
-  }
-#define BN_PH_DECL unsigned long long ph_[BN_PH_N] = {0}, pt_ = __builtin_readcyclecounter();
-#define BN_PH(i) { const unsigned long long n_ = __builtin_readcyclecounter(); ph_[i] += n_ - pt_; pt_ = n_; }
-#define BN_PH_FLUSH if ((threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < BN_PH_N; ++i_) atomicAdd(&bn_phase_clk[i_], ph_[i_]); atomicAdd(&bn_phase_clk[BN_PH_N], 1ull); }
-#else
-#define BN_PH_DEFINE_READER(NAME)
-#define BN_PH_DECL
-#define BN_PH(i)
-#define BN_PH_FLUSH
-#endif
-
-// In-kernel clock stamps, compiled only into the diagnostic library built by profiles/clock_probe.py (-DBN_CLOCK_STAMP):
-// wave 0 of every workgroup stamps s_memtime (shader clock) and s_memrealtime (100 MHz) at entry and exit; the quotient of
-// the two differences is the clock the chip holds under this kernel (MI355X_MICROARCH.md, DVFS give-back item 6).  The stamps
-// go to a buffer nothing else reads; no output depends on them.
-#ifdef BN_CLOCK_STAMP
-#define BN_CLK_N 8192
-#define BN_CLK_DEFINE(NAME)                                                                                    \
-  static __device__ unsigned long long bn_clk_buf[BN_CLK_N][2];                                               \
-  extern "C" int NAME(unsigned long long *out, int n) {                                                        \
-    if (n > BN_CLK_N) n = BN_CLK_N;                                                                            \
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(bn_clk_buf), sizeof(unsigned long long) * 2 * n) == hipSuccess ? 0 : -1; \
-  }
-#define BN_CLK_BEGIN const unsigned long long clk0_ = __builtin_amdgcn_s_memtime(), clk1_ = __builtin_amdgcn_s_memrealtime();
-#define BN_CLK_END                                                                                             \
-  if (threadIdx.x == 0 && blockIdx.x < BN_CLK_N) {                                                             \
-    bn_clk_buf[blockIdx.x][0] = __builtin_amdgcn_s_memtime() - clk0_;                                          \
-    bn_clk_buf[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime() - clk1_;                                      \
-  }
-#else
-#define BN_CLK_DEFINE(NAME)
-#define BN_CLK_BEGIN
-#define BN_CLK_END
-#endif
-
-// Per-wave event timeline, compiled only into the diagnostic library built by profiles/simd_timeline.py (-DBN_TIMELINE):
-// every wave of the first BN_TL_BLOCKS workgroups stamps s_memtime at the phase boundaries of the trunk into an LDS log
-// (a region the trunk does not use) and dumps it to a buffer nothing else reads; word 0 of a wave's log is its HW_ID
-// (which SIMD it sits on).  No output depends on the stamps; the product build executes none of this.
-#ifdef BN_TIMELINE
-#define BN_TL_BLOCKS 8
-#define BN_TL_EVENTS 112
-static __device__ unsigned long long bn_tl_buf[BN_TL_BLOCKS][8][BN_TL_EVENTS];
-#define BN_TL_DEFINE_READER(NAME)                                                                              \
-  extern "C" int NAME(unsigned long long *out) {                                                               \
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(bn_tl_buf), sizeof(unsigned long long) * BN_TL_BLOCKS * 8 * BN_TL_EVENTS) == hipSuccess ? 0 : -1; \
-  }
-// log = LDS pointer to this wave's BN_TL_EVENTS slots; event code in the top byte
-#define BN_TL_DECL(LDSBASE) unsigned long long *tl_log_ = (unsigned long long *)(LDSBASE) + (threadIdx.x >> 6) * BN_TL_EVENTS; int tl_n_ = 1; \
-  if ((threadIdx.x & 63) == 0) tl_log_[0] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-#define BN_TL(ev) { if ((threadIdx.x & 63) == 0 && tl_n_ < BN_TL_EVENTS) tl_log_[tl_n_] = ((unsigned long long)(ev) << 56) | (__builtin_amdgcn_s_memtime() & 0x00ffffffffffffffull); ++tl_n_; }
-#define BN_TL_DUMP { if (blockIdx.x < BN_TL_BLOCKS && (threadIdx.x & 63) == 0) { const int w_ = threadIdx.x >> 6; const int n_ = tl_n_ < BN_TL_EVENTS ? tl_n_ : BN_TL_EVENTS; \
-    for (int i_ = 0; i_ < BN_TL_EVENTS; ++i_) bn_tl_buf[blockIdx.x][w_][i_] = i_ < n_ ? tl_log_[i_] : 0ull; } }
-#else
-#define BN_TL_DEFINE_READER(NAME)
-#define BN_TL_DECL(LDSBASE)
-#define BN_TL(ev)
-#define BN_TL_DUMP
-#endif
+#include "instrument.h"
 
 // Stash traffic is streaming (written once here, read once by a later kernel) and several times larger than the
 // packed weights every workgroup re-reads from L2: non-temporal stores / loads keep it from evicting the weights.
@@ -155,7 +83,6 @@ template <> __device__ __forceinline__ f32x8 lds_frag<float>(const float *p) {
   f32x8 r = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
   return r;
 }
-template <typename T> __device__ __forceinline__ typename Elem<T>::frag gld_frag(const T *p) { return lds_frag<T>(p); }
 
 // acc[nt][mt] += W_packed(this wave's tiles) x B(lds).  `wp` points at the packed block of the wave's first
 // n-tile for this K segment; consecutive n-tiles are KS*512 elements apart.
@@ -228,15 +155,6 @@ __device__ __forceinline__ void pp_signal(int *flag, int lane) {
 // (config 3: -3.7 %), backward chain -1.3 % (-2.7 %) - and the inference forward +38 %, the adjoint chains +19 ... 25 % (they
 // spill with it): a property of the kernel instantiation, hence carried by its depth constant.
 #define BN_GEMM_AFFINE 64
-// BN_PP_NKS or-ed into a depth: the number of k-steps is a compile-time constant (bits 8 and up; the caller guarantees nks ==
-// that number) and the range is straight-line code - no clamps, no tail steps.  The barrier-free trunks' half-GEMMs (16 k-steps:
-// NT == 2 means F = 512) use it: in the looped form their tail steps copied the accumulator set (~70 v_mov_b64 per half-GEMM,
-// profiles/r04_isa_scan.txt).  Round 4 ablation item 20, adopted in round 5: training forward -3.8 %, sigma-only forward -8.6 %.
-#ifdef BN_PP_LOOP_NKS      // A/B switch (results unchanged): the looped form of rounds 1-4
-#define BN_PP_NKS 0
-#else
-#define BN_PP_NKS (16 << 8)
-#endif
 template <typename T, bool TRAIN_FWD> struct FwdDepth { static constexpr int value = 4; };
 template <> struct FwdDepth<bf16, true> { static constexpr int value = BN_FWD_DEPTH_TRAIN | BN_GEMM_AFFINE; };
 template <> struct FwdDepth<f16, true> { static constexpr int value = BN_FWD_DEPTH_TRAIN | BN_GEMM_AFFINE; };
@@ -247,13 +165,13 @@ template <typename T> struct BwdDepth { static constexpr int value = Elem<T>::kF
 // (round 4) measured slower wherever tried: the GEMM alone in a kernel 42 vs 35 cycles per MFMA with one wave
 // per SIMD and 78 vs 56 with two (profiles/r04_probe_gemm_rate.txt), the training forward +1 %, the backward chain +5 %
 // (profiles/r04_ablation.txt).
+// The looped form: k-steps [ks0, ks0 + nks) of a packed matrix whose n-tiles are KS k-steps apart, nks a run-time number.
+// DEPTH_ = the prefetch depth (FwdDepth / BwdDepth), with the flag BN_GEMM_AFFINE or-ed in for the one-base-per-block k-loop.
 template <typename T, int MT, int NTW, int DEPTH_, typename Side>
 __device__ __forceinline__ void gemm_range(f32x16 (&acc)[NTW][MT], const T *__restrict__ wp, int KS, int ks0, int nks, const T *bsrc,
                                            int ldb, int lane, Side &side) {
-  // k-steps [ks0, ks0 + nks) of a packed matrix whose n-tiles are KS k-steps apart
   constexpr int DEPTH = DEPTH_ & (BN_GEMM_AFFINE - 1);
   constexpr bool AFFINE = (DEPTH_ & BN_GEMM_AFFINE) != 0;
-  constexpr int NKS = DEPTH_ >> 8;      // experiment: a compile-time number of k-steps (the caller guarantees nks == NKS): straight-line code, no tail
   typedef typename Elem<T>::frag frag;
   static_assert(DEPTH % 2 == 0, "side jobs rely on an even pipeline depth");
   const int r = lane & 31, h = lane >> 5;
@@ -270,7 +188,7 @@ __device__ __forceinline__ void gemm_range(f32x16 (&acc)[NTW][MT], const T *__re
 #ifdef BN_PROBE_NO_A
         if (ks >= ks0 + DEPTH) { asm volatile("" : "+v"(a[nt])); continue; }
 #endif
-        a[nt] = gld_frag<T>(wl + ((size_t)nt * KS + ks) * 512);
+        a[nt] = lds_frag<T>(wl + ((size_t)nt * KS + ks) * 512);
       }
     }
   };
@@ -299,34 +217,6 @@ __device__ __forceinline__ void gemm_range(f32x16 (&acc)[NTW][MT], const T *__re
   loadB(Bc, ks0);
   __builtin_amdgcn_sched_barrier(0);
   int ks = ks0;
-  if constexpr (NKS > 0) {
-    const T *bm[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) bm[mt] = bl + (size_t)mt * 32 * ldb + (size_t)ks0 * 16;
-#pragma unroll
-    for (int j = 0; j < NKS; ++j) {
-      frag Bn[MT];
-      if (j + 1 < NKS) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) Bn[mt] = lds_frag<T>(bm[mt] + (j + 1) * 16);
-      }
-#pragma unroll
-      for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) mma32(acc[nt][mt], A[j % DEPTH][nt], Bc[mt]);
-      if (j + 1 < NKS) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) Bc[mt] = Bn[mt];
-      }
-      if (j + DEPTH < NKS) {
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) A[j % DEPTH][nt] = gld_frag<T>(wl + ((size_t)nt * KS + ks0 + j + DEPTH) * 512);
-      }
-      side.at(j & 1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    return;
-  }
   if constexpr (AFFINE) {
   // Whole blocks of DEPTH k-steps: the LDS fragment addresses of a block are ONE base per point tile (advanced once per block)
   // plus compile-time offsets - the look-ahead of a range's last step reads the 16 columns behind the range (row pad / the
@@ -404,11 +294,7 @@ __device__ __forceinline__ void gemm_fixed(f32x16 (&acc)[NTW][MT], const T *__re
   const auto rs = stash_rsrc(wp);
   const int voff = lane * 16;
   auto ldA = [&](int nt, int ks) {
-#ifdef BN_NO_BUFW      // A/B switch (results unchanged): global loads with 64-bit vector addresses, as in rounds 1-4
-    return gld_frag<T>(wp + (size_t)lane * 8 + ((size_t)nt * KS + ks0 + ks) * 512);
-#else
     return __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (nt * KS + ks0 + ks) * (512 * (int)sizeof(T)), 0));
-#endif
   };
   frag A[DEPTH][NTW], Bc[MT];
 #pragma unroll
@@ -448,48 +334,35 @@ __device__ __forceinline__ void gemm_fixed(f32x16 (&acc)[NTW][MT], const T *__re
     }
   }
 }
-// the barrier-free trunks' layer GEMM: 32 k-steps, hand-over behind the 16th
-template <typename T, int MT, int NTW, int DEPTH, int NKS, int MID, typename Mid>
-__device__ __forceinline__ void gemm_trunk(f32x16 (&acc)[NTW][MT], const T *__restrict__ wp, int KS, const T *bsrc, int ldb, int lane,
-                                           Mid &&mid) {
-  gemm_fixed<T, MT, NTW, DEPTH, NKS, MID>(acc, wp, KS, 0, bsrc, ldb, lane, mid);
-}
+// the looped form over all KS k-steps of a packed matrix, with and without a side job (two overloads that each call
+// gemm_range themselves: with a defaulted argument, or one overload forwarding to the other, hipcc schedules callers differently)
 template <typename T, int MT, int NTW, int DEPTH, typename Side>
 __device__ __forceinline__ void gemm_seg(f32x16 (&acc)[NTW][MT], const T *__restrict__ wp, int KS, const T *bsrc, int ldb,
                                          int lane, Side &side) {
-  gemm_range<T, MT, NTW, DEPTH, Side>(acc, wp, KS, 0, KS, bsrc, ldb, lane, side);
+  gemm_range<T, MT, NTW, DEPTH>(acc, wp, KS, 0, KS, bsrc, ldb, lane, side);
 }
 template <typename T, int MT, int NTW, int DEPTH>
 __device__ __forceinline__ void gemm_seg(f32x16 (&acc)[NTW][MT], const T *__restrict__ wp, int KS, const T *bsrc, int ldb,
                                          int lane) {
   NoSide none;
-  gemm_range<T, MT, NTW, DEPTH, NoSide>(acc, wp, KS, 0, KS, bsrc, ldb, lane, none);
+  gemm_range<T, MT, NTW, DEPTH>(acc, wp, KS, 0, KS, bsrc, ldb, lane, none);
 }
 
-// A full-width product under barriers (head passes, the backward's top layer).  HOT = the F = 512 instantiation of a 16-bit mode
-// (NT == 2): its k-step counts are 32 (F / 16) or 16 (a single head's 256 hidden columns) - straight-line streams; every other
-// shape keeps the looped form.
-template <typename T, int MT, int NTW, int DP, bool HOT>
-__device__ __forceinline__ void gemm_full(f32x16 (&acc)[NTW][MT], const T *__restrict__ wp, int KS, const T *bsrc, int ldb, int lane) {
-#ifndef BN_NO_FIXED_FULL      // A/B switch (results unchanged): the looped form everywhere outside the trunks (round 4)
-  if constexpr (HOT && sizeof(T) == 2) {
-    constexpr int D = (DP & (BN_GEMM_AFFINE - 1)) < 2 ? 2 : (DP & (BN_GEMM_AFFINE - 1));
-    if (KS == 32) { gemm_fixed<T, MT, NTW, D, 32, 0>(acc, wp, KS, 0, bsrc, ldb, lane, NoMid()); return; }
-    if (KS == 16) { gemm_fixed<T, MT, NTW, D, 16, 0>(acc, wp, KS, 0, bsrc, ldb, lane, NoMid()); return; }
-  }
-#endif
-  gemm_seg<T, MT, NTW, DP>(acc, wp, KS, bsrc, ldb, lane);
-}
-// the F = 512 trunk product (32 k-steps) of the analytic-normal chains with a riding stash copy (field_adjoint / field_adjbwd)
-template <typename T, int MT, int NTW, int DP, bool HOT, typename Side>
-__device__ __forceinline__ void gemm_full32(f32x16 (&acc)[NTW][MT], const T *__restrict__ wp, int KS, const T *bsrc, int ldb, int lane,
-                                            Side &side) {
-#ifndef BN_ADJ_LOOP      // A/B switch (results unchanged): the looped form (round 4); straight-line: adjoint chain -8.6 %, r05 item 7
+// A full-width product under barriers (head passes, the backward's top layer, the trunk product of the analytic-normal chains).
+// HOT = the F = 512 instantiation of a 16-bit mode (NT == 2): its k-step counts are 32 (F / 16) or 16 (a single head's 256
+// hidden columns) - straight-line streams (profiles/r05_ablation.txt items 2 and 7; the looped form of round 4 there: adjoint
+// chain +8.6 %); every other shape keeps the looped form.  A side job (the riding stash copy of field_adjoint) is sized for the
+// F-wide product (TileCopyExact): with one, only the 32-step stream is compiled.
+template <typename T, int MT, int NTW, int DP, bool HOT, typename Side = NoSide>
+__device__ __forceinline__ void gemm_full(f32x16 (&acc)[NTW][MT], const T *__restrict__ wp, int KS, const T *bsrc, int ldb, int lane,
+                                          Side &&side = Side()) {
   if constexpr (HOT && sizeof(T) == 2) {
     constexpr int D = (DP & (BN_GEMM_AFFINE - 1)) < 2 ? 2 : (DP & (BN_GEMM_AFFINE - 1));
     if (KS == 32) { gemm_fixed<T, MT, NTW, D, 32, 0>(acc, wp, KS, 0, bsrc, ldb, lane, NoMid(), side); return; }
+    if constexpr (std::is_same<std::decay_t<Side>, NoSide>::value) {
+      if (KS == 16) { gemm_fixed<T, MT, NTW, D, 16, 0>(acc, wp, KS, 0, bsrc, ldb, lane, NoMid()); return; }
+    }
   }
-#endif
   gemm_seg<T, MT, NTW, DP>(acc, wp, KS, bsrc, ldb, lane, side);
 }
 
@@ -529,20 +402,7 @@ __device__ __forceinline__ void st_frag(float *p, const f32x8 &o) {
   stash_store((f32x4 *)p, f32x4{o[0], o[1], o[2], o[3]});
   stash_store((f32x4 *)(p + 4), f32x4{o[4], o[5], o[6], o[7]});
 }
-__device__ __forceinline__ void st8(bf16 *p, const float (&v)[8]) {
-  bf16x8 o;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = (bf16)v[i];
-  stash_store((bf16x8 *)p, o);
-}
-__device__ __forceinline__ void st8(f16 *p, const float (&v)[8]) {
-  const f32x8 f = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
-  stash_store((f16x8 *)p, __builtin_convertvector(f, f16x8));
-}
-__device__ __forceinline__ void st8(float *p, const float (&v)[8]) {
-  stash_store((f32x4 *)p, f32x4{v[0], v[1], v[2], v[3]});
-  stash_store((f32x4 *)(p + 4), f32x4{v[4], v[5], v[6], v[7]});
-}
+template <typename T> __device__ __forceinline__ void st8(T *p, const float (&v)[8]) { st_frag(p, cvt8(T(), v)); }
 __device__ __forceinline__ void ld8(const bf16 *p, float (&v)[8]) {
   const bf16x8 o = stash_load((const bf16x8 *)p);
 #pragma unroll

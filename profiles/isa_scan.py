@@ -22,12 +22,10 @@ from brdf_nerf_amd import build as B  # noqa: E402
 
 def main():
     src, pat = sys.argv[1], sys.argv[2]
-    defs = [a for a in sys.argv[3:] if a.startswith("-D")]
+    defs = [a[2:] for a in sys.argv[3:] if a.startswith("-D")]
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
-        cmd = [B.HIPCC] + B.FLAGS + list(B.FILE_FLAGS.get(src, ())) + defs + ["-x", "hip", "--cuda-device-only", "-S",
-                                                                            os.path.join(B.CSRC, src), "-o", out]
-        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+        subprocess.run(B.compile_command(os.path.join(B.CSRC, src), out, defs, asm=True), check=True, stderr=subprocess.DEVNULL)
         text = open(out).read()
     for k in re.split(r"\n(?=_Z[\w]+:\s*; @)", text):
         m = re.match(r"(_Z[\w]+):", k)

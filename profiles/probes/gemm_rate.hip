@@ -19,7 +19,7 @@ __device__ __forceinline__ void wstream_start(typename Elem<T>::frag (&A)[DEPTH]
 #pragma unroll
   for (int d = 0; d < DEPTH; ++d)
 #pragma unroll
-    for (int nt = 0; nt < NTW; ++nt) A[d][nt] = gld_frag<T>(wl + ((size_t)nt * KS + k0 + d) * 512);
+    for (int nt = 0; nt < NTW; ++nt) A[d][nt] = lds_frag<T>(wl + ((size_t)nt * KS + k0 + d) * 512);
 }
 // k-steps [k0, k0 + nks) of the packed matrix wp (n-tiles KS k-steps apart); the stream continues at k-step k0n of matrix wpn
 // (n-tiles KSn apart).  The last segment of a stream passes its own matrix and k0n = k0 + nks - DEPTH (a harmless re-read).
@@ -55,7 +55,7 @@ __device__ __forceinline__ void gemm_stream(f32x16 (&acc)[NTW][MT], typename Ele
       const T *pw = cur ? wl : wln;
       const int K2 = cur ? KS : KSn, ki = cur ? kk : k0n + (kk - kend);
 #pragma unroll
-      for (int nt = 0; nt < NTW; ++nt) A[d][nt] = gld_frag<T>(pw + ((size_t)nt * K2 + ki) * 512);
+      for (int nt = 0; nt < NTW; ++nt) A[d][nt] = lds_frag<T>(pw + ((size_t)nt * K2 + ki) * 512);
       __builtin_amdgcn_sched_barrier(0);
     }
   }

@@ -1,6 +1,6 @@
 """Per-SIMD timeline of the training forward's trunk (diagnostic build, -DBN_TIMELINE).
 
-Every wave of the first 8 workgroups stamps s_memtime at the phase boundaries of the trunk (field_kernels.h BN_TL); the script
+Every wave of the first 8 workgroups stamps s_memtime at the phase boundaries of the trunk (csrc/instrument.h BN_TL); the script
 prints, for the two waves of each SIMD (wave w and w + 4: HW_ID confirms the SIMD), when each was in a GEMM half and when in an
 epilogue pass, per layer, in shader cycles from the workgroup's first stamp - and the share of the trunk during which exactly
 one / both / neither of the two waves was inside a GEMM.
@@ -25,8 +25,7 @@ def build_tl(defines, tag):
     objdir = os.path.join(B.HERE, "build")
     objs = [os.path.join(objdir, os.path.basename(s) + ".o") for s in B.sources() if not s.endswith("field_fwd.hip")]
     obj = os.path.join(objdir, f"field_fwd.hip.timeline{tag}.o")
-    subprocess.check_call([B.HIPCC] + B.FLAGS + list(B.FILE_FLAGS.get("field_fwd.hip", ())) + ["-DBN_TIMELINE"] + ["-D" + d for d in defines] +
-                          ["-x", "hip", "-c", os.path.join(B.CSRC, "field_fwd.hip"), "-o", obj])
+    subprocess.check_call(B.compile_command(os.path.join(B.CSRC, "field_fwd.hip"), obj, ["BN_TIMELINE"] + list(defines)))
     lib = os.path.join(objdir, f"libbn_timeline{tag}.so")
     subprocess.check_call([B.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [obj])
     return lib

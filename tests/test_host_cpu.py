@@ -55,6 +55,26 @@ def test_release_library_has_no_diagnostic_switches():
     assert _lib.lib().bn_build_flags() == b""
 
 
+def test_every_switch_the_sources_test_is_in_the_catalogue():
+    """csrc/diag.h lists every -D switch once (BN_SWITCH(NAME)); bn_build_flags() reports from that list.  A name that a
+    preprocessor conditional tests and the list lacks would make a variant library report itself as the product build."""
+    csrc = os.path.join(ROOT, "brdf_nerf_amd", "csrc")
+    listed = set(re.findall(r"^BN_SWITCH\((\w+)\)", open(os.path.join(csrc, "diag.h")).read(), re.M))
+    assert len(listed) > 10
+    not_switches = {"BN_SOURCE_HASH",      # the build stamps it into error.cpp
+                    "BN_SWITCH"}           # diag.h's own list / defaults selector
+    tested = {}
+    for name in sorted(n for n in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, n))):
+        text = re.sub(r"\\\n", " ", open(os.path.join(csrc, name)).read())
+        for line in text.splitlines():
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if m:
+                for ident in re.findall(r"\b(BN_[A-Z0-9_]+|SKINNY_SPLITS)\b", m.group(2).split("//")[0]):
+                    tested.setdefault(ident, name)
+    missing = {k: v for k, v in tested.items() if k not in listed | not_switches}
+    assert not missing, f"tested by a conditional but not in diag.h: {missing}"
+
+
 def test_library_carries_the_hash_of_the_sources_beside_it(tmp_path, monkeypatch):
     """build() decides by content, not mtimes - the library holds the sha256 prefix of the sources it was
     compiled from; the loader refuses a library built from other sources."""
