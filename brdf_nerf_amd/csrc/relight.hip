@@ -1,0 +1,170 @@
+// Ray-level shading of ONE set of composited sums under MANY sun / view directions, forward only: relighting a rendered view and
+// the BRDF lobe of a pixel without another field pass.
+//
+// With one BRDF per ray (MultiBRDF == 0) and no sun-visibility pass the colour of a ray is a function of the composited sums
+// acc [R][C], wsum [R], the view direction and the sun direction (ray_tail.hip; models/spsbrdfnerf.py:259-357), and none of the
+// sums depends on the sun.  K directions therefore cost one geometry pass and this kernel: a lane owns one ray, prepares its row
+// once (composited albedo, normalised composited normal, BRDF parameters) and walks a tile of directions.  The directions are
+// the same for every lane of a wave: inside the loop they are read with s_load_dwordx2 + s_load_dword into SGPRs (the direction and
+// output pointers are __restrict__ kernel parameters, see the kernel) and cost no vector registers or vector-memory waits.  The stores
+// to rgb[k][ray][0:3] are contiguous across the lanes of a wave (768 B per direction).  Grid = ray blocks x direction tiles.
+// Replaces eval.py's eval_pixel_variedvw / get_view_dirs loop and create_dsm.py:44-77 (rays[:, 8:11] = sun, render again).
+#include "common.h"
+#include "brdfnerf_hip.h"
+#include "prof.h"
+// (no FMA contraction, like brdf.hip and ray_tail.hip: one direction must round like bn_ray_shade_loss)
+#pragma clang fp contract(off)
+#include "brdf_eval.h"
+
+namespace {
+
+struct RelightArgs {
+  bn_shade_desc d;
+  const float *acc, *wsum, *rays_d;
+  int64_t rd_stride;
+  int64_t R;
+  int32_t K, ktile;
+};
+
+// KIND: BN_SHADE_*.  MASK: which of the BRDF's parameter heads exist (bit 0 p0, bit 1 p1, bit 2 p2 - or, for RPV, rhoc = albedo_s):
+// a compile-time constant, so that the nullable-pointer arguments of the BRDF bodies fold away and the parameters stay in
+// registers (a run-time select between a local array and nullptr forces the array into scratch).
+// sun / view [K][3] (view nullptr: -rays_d of the ray, sun mode; else the lobe's view directions) and rgb / brdf [K][R][3] (brdf
+// nullable) are kernel parameters of their own, __restrict__: only then can the compiler know that the stores of the direction loop
+// do not touch the directions, and read sun[k] / view[k] through the scalar cache.
+template <int KIND, int MASK> __global__ __launch_bounds__(64)
+void ray_shade_dirs_kernel(const RelightArgs A, const float *__restrict__ sun, const float *__restrict__ view, float *__restrict__ rgb_out,
+                           float *__restrict__ brdf_out) {
+  const int64_t ray = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (ray >= A.R) return;
+  const bn_shade_desc &q = A.d;
+  const float *acc = A.acc + ray * q.C;
+  const float ws = A.wsum[ray];
+  const float pad = q.rgb_padding;
+  const bool has_n = q.ch_normal >= 0;
+  // ---- the ray's row, once: composited albedo sum_s w (albedo (1 + 2 pad) - pad)   (:270, :275)
+  float w[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) w[c] = acc[c] * (1.f + 2.f * pad) - pad * ws;
+  V3<float> ns = {0.f, 0.f, 1.f}, vray = {0.f, 0.f, 1.f};
+  float p0[3] = {0.f, 0.f, 0.f}, p1[3] = {0.f, 0.f, 0.f}, p2[3] = {0.f, 0.f, 0.f};
+  if (KIND != BN_SHADE_LAMBERT) {
+    const float *an = acc + q.ch_normal;       // l2_normalize (train_utils.py:28-33) of the composited normal
+    const float nrm = sqrtf(clamp_min_(an[0] * an[0] + an[1] * an[1] + an[2] * an[2], 1.1920928955078125e-07f));
+    ns = {an[0] / nrm, an[1] / nrm, an[2] / nrm};
+    if (!view) {
+      const float *rd = A.rays_d + ray * A.rd_stride;
+      vray = {-rd[0], -rd[1], -rd[2]};
+    }
+    if (KIND == BN_SHADE_MICROFACET) {
+      p0[0] = acc[q.ch_p0];
+    } else {
+      const int n2 = KIND == BN_SHADE_HAPKE ? 1 : 3;          // Hapke's theta is one channel wide
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        if (MASK & 1) p0[c] = acc[q.ch_p0 + c];
+        if (MASK & 2) p1[c] = acc[q.ch_p1 + c];
+        if ((MASK & 4) && c < n2) p2[c] = (KIND == BN_SHADE_RPV && q.rhoc_is_albedo) ? w[c] : acc[q.ch_p2 + c];   // funcH == 2 (:288-291)
+      }
+    }
+  }
+  // ---- the tile of directions: k is the same in every lane, sun[k] / view[k] come through the scalar cache
+  const int k0 = (int)blockIdx.y * A.ktile;
+  const int k1 = min(A.K, k0 + A.ktile);
+  const int64_t plane = A.R * 3;
+  for (int k = k0; k < k1; ++k) {
+    const float *sk = sun + (int64_t)k * 3;
+    const V3<float> l = {sk[0], sk[1], sk[2]};
+    V3<float> v = vray;
+    if (view) {
+      const float *vk = view + (int64_t)k * 3;
+      v = {vk[0], vk[1], vk[2]};
+    }
+    // upward normal: |sun_z| (spsbrdfnerf.py:260-264), else 1
+    const float irr = (q.cos_irradiance && has_n) ? fabsf(l.z) : 1.f;
+    float out[3];
+    if (KIND == BN_SHADE_LAMBERT) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) out[c] = w[c];
+    } else if (KIND == BN_SHADE_RPV) {
+      rpv_eval<float>(l, v, ns, w, (MASK & 1) ? p0 : nullptr, (MASK & 2) ? p1 : nullptr, (MASK & 4) ? p2 : nullptr, out, nullptr);
+    } else if (KIND == BN_SHADE_HAPKE) {
+      hapke_eval<float>(l, v, ns, w, (MASK & 1) ? p0 : nullptr, (MASK & 2) ? p1 : nullptr, (MASK & 4) ? p2 : nullptr, q.hpk_scl,
+                        q.shell, out, nullptr);
+    } else {
+      microfacet_eval<float>(l, v, ns, w, p0[0], q.f0, out, nullptr);
+    }
+    float *rgb = rgb_out + (int64_t)k * plane + ray * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float x = irr * out[c];            // (irr == 1 without the cosine term: exact)
+      rgb[c] = isnan(x) ? x : fminf(fmaxf(x, 0.f), 1.f);
+    }
+    if (brdf_out) {
+      float *b = brdf_out + (int64_t)k * plane + ray * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) b[c] = out[c];
+    }
+  }
+}
+
+template <int KIND> void launch_masked(int mask, dim3 grid, hipStream_t st, const RelightArgs &a, const float *sun, const float *view,
+                                       float *rgb, float *brdf) {
+  switch (mask) {
+    case 0: ray_shade_dirs_kernel<KIND, 0><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 1: ray_shade_dirs_kernel<KIND, 1><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 2: ray_shade_dirs_kernel<KIND, 2><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 3: ray_shade_dirs_kernel<KIND, 3><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 4: ray_shade_dirs_kernel<KIND, 4><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 5: ray_shade_dirs_kernel<KIND, 5><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 6: ray_shade_dirs_kernel<KIND, 6><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    default: ray_shade_dirs_kernel<KIND, 7><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+  }
+}
+
+}  // namespace
+
+extern "C" int bn_ray_shade_dirs(const bn_shade_desc *desc, const float *acc, const float *wsum, const float *rays_d,
+                                 int64_t rd_stride, const float *sun, const float *view, int64_t R, int32_t K, float *rgb,
+                                 float *brdf, void *stream) {
+  BN_REQUIRE(desc && acc && wsum && sun && rgb && R > 0 && K > 0, "ray_shade_dirs: null argument");
+  const bn_shade_desc &q = *desc;
+  BN_REQUIRE(q.C >= 4 && q.C <= BN_MAX_CH, "ray_shade_dirs: C=%d unsupported", q.C);
+  BN_REQUIRE(q.kind >= BN_SHADE_LAMBERT && q.kind <= BN_SHADE_MICROFACET, "ray_shade_dirs: kind=%d", q.kind);
+  BN_REQUIRE(!q.irr, "ray_shade_dirs: a per-ray irradiance of the sun pass depends on the sun direction (not relightable)");
+  auto in_range = [&](int ch, int n) { return ch < 0 || (ch >= 4 && ch + n <= q.C); };
+  BN_REQUIRE(in_range(q.ch_normal, 3), "ray_shade_dirs: normal channel %d outside [4, %d)", q.ch_normal, q.C);
+  if (q.kind != BN_SHADE_LAMBERT) {
+    BN_REQUIRE(q.ch_normal >= 4 && (rays_d || view), "ray_shade_dirs: BRDF shading needs a normal field and the ray or view directions");
+    const int n2 = q.kind == BN_SHADE_HAPKE ? 1 : 3;
+    const int n0 = q.kind == BN_SHADE_MICROFACET ? 1 : 3;
+    BN_REQUIRE(in_range(q.ch_p0, n0) && in_range(q.ch_p1, 3) && in_range(q.ch_p2, n2), "ray_shade_dirs: parameter channels (%d, %d, %d) outside [4, %d)",
+               q.ch_p0, q.ch_p1, q.ch_p2, q.C);
+    BN_REQUIRE(q.kind != BN_SHADE_MICROFACET || q.ch_p0 >= 4, "ray_shade_dirs: microfacet needs the roughness channel");
+    BN_REQUIRE(q.kind != BN_SHADE_HAPKE || q.ch_p0 >= 4 || (q.shell >= 1 && q.shell <= 3), "ray_shade_dirs: Hapke without b needs shell_hapke in {1,2,3}");
+  }
+  BN_REQUIRE(R <= (int64_t)64 * 0x7fffffff, "ray_shade_dirs: R=%lld too large", (long long)R);
+  RelightArgs a;
+  a.d = q; a.acc = acc; a.wsum = wsum; a.rays_d = rays_d; a.rd_stride = rd_stride; a.R = R; a.K = K;
+  // Direction tile: as long as possible (the ray's row is loaded and prepared once per tile) while ray blocks x tiles still give
+  // every CU several waves - an image has thousands of ray blocks and takes all its directions in one tile (up to 32), a lobe has
+  // one ray block and tens of thousands of directions.  Every (direction, ray) is computed on its own: the tiling changes no bit.
+  const int64_t blocks = ceil_div64(R, 64);
+  int64_t kt = (int64_t)K * blocks / 2048;
+  kt = kt < 1 ? 1 : (kt > 32 ? 32 : kt);
+  const int64_t need = ceil_div64(K, 65535);               // gridDim.y <= 65535
+  if (kt < need) kt = need;
+  a.ktile = (int32_t)kt;
+  const dim3 grid((unsigned)blocks, (unsigned)ceil_div64(K, kt));
+  hipStream_t st = (hipStream_t)stream;
+  BnProfScope prof_(BN_K_BRDF, st);
+  const int mask = (q.ch_p0 >= 0 ? 1 : 0) | (q.ch_p1 >= 0 ? 2 : 0) | ((q.ch_p2 >= 0 || (q.kind == BN_SHADE_RPV && q.rhoc_is_albedo)) ? 4 : 0);
+  switch (q.kind) {
+    case BN_SHADE_LAMBERT: ray_shade_dirs_kernel<BN_SHADE_LAMBERT, 0><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case BN_SHADE_RPV: launch_masked<BN_SHADE_RPV>(mask, grid, st, a, sun, view, rgb, brdf); break;
+    case BN_SHADE_HAPKE: launch_masked<BN_SHADE_HAPKE>(mask, grid, st, a, sun, view, rgb, brdf); break;
+    default: ray_shade_dirs_kernel<BN_SHADE_MICROFACET, 1><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+  }
+  BN_LAUNCH_CHECK("ray_shade_dirs");
+  return 0;
+}

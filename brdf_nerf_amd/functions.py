@@ -676,6 +676,32 @@ def ray_shade_loss(desc, acc, wsum, depth, var, rays_d, sun_d, rgbs, bufs=None, 
     return o
 
 
+def ray_shade_dirs(desc, acc, wsum, rays_d, sun, view=None, rgb=None, brdf=None, want_brdf=False):
+    """The shading of ray_shade_loss under K directions in one launch (bn_ray_shade_dirs), forward only.  acc (R,C), wsum (R,);
+    rays_d (R,3) view with unit inner stride; sun (K,3); view (K,3) or None (-rays_d).  -> rgb (K,R,3) and brdf (K,R,3) or None
+    (the value before irradiance and clamp; with `brdf` given or want_brdf)."""
+    R, Cc = acc.shape
+    K = sun.shape[0]
+    for t in (acc, wsum, sun) + (() if view is None else (view,)):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    assert wsum.numel() == R and sun.shape == (K, 3) and (view is None or view.shape == (K, 3)) and desc.C == Cc
+    rdp, rds = None, 0
+    if rays_d is not None:
+        assert rays_d.is_cuda and rays_d.dtype == torch.float32 and rays_d.shape == (R, 3)
+        if rays_d.stride(1) != 1:
+            rays_d = rays_d.contiguous()
+        rdp, rds = C.c_void_p(rays_d.data_ptr()), rays_d.stride(0)
+    if rgb is None:
+        rgb = torch.empty((K, R, 3), dtype=torch.float32, device=acc.device)
+    if brdf is None and want_brdf:
+        brdf = torch.empty((K, R, 3), dtype=torch.float32, device=acc.device)
+    for t in (rgb, brdf):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.shape == (K, R, 3))
+    L.check(L.lib().bn_ray_shade_dirs(C.byref(desc), _p(acc), _p(wsum), rdp, rds, _p(sun), _p(view), R, K, _p(rgb), _p(brdf),
+                                      _stream()), "bn_ray_shade_dirs")
+    return rgb, brdf
+
+
 def sample_brdf(desc, X, rays, n1, S1, S2, out, backward_of=None, sun_col=8):
     """Per-sample BRDF of --MultiBRDF on stored field-output rows (bn_sample_brdf_forward / _backward).  X (N, C) rows of which the
     first n1 are S1 per ray and the rest S2 per ray; rays (R, >= 6) fp32 rows (sun at sun_col, < 0: ones).  Forward: `out` (N, 4) or

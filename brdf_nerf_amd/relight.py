@@ -1,0 +1,190 @@
+"""Relighting a rendered view and the BRDF lobe of a pixel from ONE geometry pass.
+
+The reference relights by writing a sun direction into the ray table and rendering again, once per direction
+(create_dsm.py:44-77: rays[:, 8:11] = sun; eval.py's eval_pixel_variedvw / get_view_dirs for the view hemisphere): every call
+evaluates the field again, which is all of the cost.  With one BRDF per ray (MultiBRDF == 0) and no sun-visibility pass the
+colour is a function of the composited sums, the view direction and the sun direction (rendering.shade_ray), and the sums do
+not depend on the sun.  So:
+
+  render_surface   the geometry half of evaluate.render_image: acc, wsum, depth of every ray of the view, kept
+  relight          K sun directions (or K (view, sun) pairs) shaded from a surface in one launch (bn_ray_shade_dirs)
+  relight_image    the two in one call
+  brdf_lobe        BRDF value and colour of chosen pixels over a grid of view directions
+  directions       the reference's (elevation, azimuth) -> unit vector convention (eval.py:300-314, create_dsm.py:48-50)
+
+Not covered, and refused by name: --MultiBRDF (shading is per sample), --sun_v analystic (the irradiance itself depends on the
+sun through a field pass), gsam_only.
+"""
+import torch
+
+from . import functions as Fn
+from .rendering import _composite_merged, _sample_passes, shade_desc
+
+# directions of one bn_ray_shade_dirs launch at most: bounds the (K, R, 3) result a launch writes when `out` lives on the host
+_TILE_BYTES = 1 << 30
+
+
+def directions(elevation_deg, azimuth_deg):
+    """Unit vectors of (elevation, azimuth) in degrees, the reference's convention (eval.py:300-314, create_dsm.py:48-50):
+    (sin az cos el, cos az cos el, sin el) - azimuth from the +y axis towards +x, elevation above the x-y plane.  The two
+    arguments broadcast; -> float32 (..., 3)."""
+    el = torch.deg2rad(torch.as_tensor(elevation_deg, dtype=torch.float64))
+    az = torch.deg2rad(torch.as_tensor(azimuth_deg, dtype=torch.float64))
+    el, az = torch.broadcast_tensors(el, az)
+    return torch.stack([torch.sin(az) * torch.cos(el), torch.cos(az) * torch.cos(el), torch.sin(el)], -1).float()
+
+
+def _check_relightable(model, args, gsam_only=False):
+    """The argument checks of the shortcut, before any device work."""
+    if int(getattr(args, "MultiBRDF", 0)) or getattr(model, "MultiBRDF", False):
+        raise NotImplementedError("relighting from composited sums does not cover --MultiBRDF 1: every sample is shaded by its own "
+                                  "BRDF, so each direction needs the per-sample outputs (render_rays per direction)")
+    if getattr(args, "sun_v", "none") == "analystic" or getattr(model, "sun_v", "none") == "analystic":
+        raise NotImplementedError("relighting from composited sums does not cover --sun_v analystic: the irradiance is the sun "
+                                  "visibility of a field pass along each sun direction (render_rays per direction)")
+    if gsam_only:
+        raise NotImplementedError("relighting does not cover gsam_only=True: the surface is composited from the merged S + G "
+                                  "sample set of the default evaluation path")
+
+
+class Surface:
+    """What the ray-level shading reads, for all R rays of a view: the composited sums acc (R, C) and wsum (R,), depth (R,),
+    the ray directions rays_d (R, 3), and the model / args / spec that name the BRDF (rendering.shade_desc).  16 MB for a
+    512 x 512 view at C = 16."""
+
+    def __init__(self, acc, wsum, depth, rays_d, model, args, spec, apply_brdf, apply_theta):
+        self.acc, self.wsum, self.depth, self.rays_d = acc, wsum, depth, rays_d
+        self.model, self.args, self.spec, self.apply_brdf, self.apply_theta = model, args, spec, apply_brdf, apply_theta
+
+    @property
+    def n_rays(self):
+        return self.acc.shape[0]
+
+    def select(self, rows):
+        """The surface of the chosen rays (rows: indices, a slice or a mask)."""
+        if not isinstance(rows, slice):
+            rows = torch.as_tensor(rows, device=self.acc.device)
+        pick = lambda t: t[rows].contiguous()
+        return Surface(pick(self.acc), pick(self.wsum), pick(self.depth), pick(self.rays_d), self.model, self.args, self.spec,
+                       self.apply_brdf, self.apply_theta)
+
+    def desc(self, apply_brdf=None, cos_irra_on=False):
+        """bn_shade_desc of this surface (the selection rules of rendering.shade())."""
+        apply_brdf = self.apply_brdf if apply_brdf is None else apply_brdf
+        if apply_brdf and not self.apply_brdf:
+            raise ValueError("this surface was rendered with apply_brdf=False: the BRDF heads were not composited")
+        return shade_desc(self.model, self.args, self.spec, apply_brdf, cos_irra_on)
+
+
+@torch.no_grad()
+def render_surface(models, args, rays, ts=None, chunk=None, apply_brdf=False, apply_theta=False, group=None, gsam_only=False,
+                   bTestNormal=False):
+    """The geometry half of evaluate.render_image: pass 1, the guided samples and the compositing of the merged sample set of
+    every ray, in chunks, WITHOUT the shading - the random stream is consumed exactly as render_rays consumes it, so after the
+    same torch.manual_seed the sums are the ones render_rays composited (and `depth` is its depth_coarse bit for bit).  Under
+    data parallelism every rank renders its contiguous share of the rays and the rows are all-gathered, as in render_image.
+    -> Surface."""
+    from .distributed import gather_rows, shard_bounds, world_info
+    model = models["coarse"]
+    _check_relightable(model, args, gsam_only)
+    rank, world = world_info(group)
+    lo, hi = shard_bounds(rays.shape[0], rank, world)
+    chunk = chunk or args.chunk
+    parts = {"acc": [], "wsum": [], "depth": []}
+    spec = None
+    for i in range(lo, hi, chunk):
+        j = min(hi, i + chunk)
+        p = _sample_passes(models, args, rays[i:j], None if ts is None else ts[i:j], "test", None, None, None, apply_brdf,
+                           bTestNormal, False, False, apply_theta)
+        _, _, _, weights, depth, acc = _composite_merged(p, args)
+        spec = p.spec
+        parts["acc"].append(acc)
+        parts["wsum"].append(weights.sum(-1))
+        parts["depth"].append(depth)
+    if spec is None:            # a rank without rays (more ranks than rays): the spec is still the model's
+        nr_lr = model.normal in ("analystic_learned", "learned")
+        nr_an = model.normal in ("analystic_learned", "analystic") or bTestNormal
+        spec = model.spec(apply_brdf, apply_theta, nr_lr, nr_an)
+    res = {}
+    for k, v in parts.items():
+        shape = (0, spec.out_channels) if k == "acc" else (0,)
+        t = torch.cat(v, 0) if v else torch.zeros(shape, dtype=torch.float32, device=rays.device)
+        res[k] = gather_rows(t, group) if world > 1 else t
+    return Surface(res["acc"].contiguous(), res["wsum"].contiguous(), res["depth"].contiguous(),
+                   rays[:, 3:6].float().contiguous(), model, args, spec, bool(apply_brdf), bool(apply_theta))
+
+
+def _dirs(d, device, K=None):
+    d = torch.as_tensor(d, dtype=torch.float32).to(device).reshape(-1, 3)
+    if K is not None and d.shape[0] == 1 and K != 1:
+        d = d.expand(K, 3)
+    return d.contiguous()
+
+
+@torch.no_grad()
+def relight(surface, sun_dirs, apply_brdf=None, cos_irra_on=False, out=None, view_dirs=None, want_brdf=False, dir_tile=None):
+    """Shade a Surface under K sun directions: -> rgb (K, R, 3), rgb[k] = what render_rays gives as rgb_coarse with
+    rays[:, 8:11] = sun_dirs[k] (same draws).  No field evaluation.
+      sun_dirs   (K, 3)
+      view_dirs  None: every ray is seen along its own -rays_d.  (K, 3) (or (1, 3)): lobe mode - direction k REPLACES the view
+                 of every ray, paired with sun_dirs[k] (sun_dirs (1, 3): one fixed sun).
+      apply_brdf / cos_irra_on  as in render_rays (apply_brdf None: as the surface was rendered)
+      out        (K, R, 3) float32 to write into, on the device or on the host
+      want_brdf  also return the BRDF value before irradiance and clamp: -> (rgb, brdf)
+      dir_tile   directions per launch (None: all at once on the device, 1 GiB of results at a time into a host `out`);
+                 every (direction, ray) is computed on its own, so the split changes no bit."""
+    dev = surface.acc.device
+    K = None if view_dirs is None else torch.as_tensor(view_dirs).reshape(-1, 3).shape[0]
+    sun = _dirs(sun_dirs, dev, K)
+    K = sun.shape[0]
+    view = None if view_dirs is None else _dirs(view_dirs, dev, K)
+    if view is not None and view.shape[0] != K:
+        raise ValueError(f"view_dirs ({view.shape[0]}) and sun_dirs ({K}) must pair up (or one of them be a single direction)")
+    R = surface.n_rays
+    desc = surface.desc(apply_brdf, cos_irra_on)
+    if out is not None and (tuple(out.shape) != (K, R, 3) or out.dtype != torch.float32):
+        raise ValueError(f"out must be float32 {(K, R, 3)}, got {out.dtype} {tuple(out.shape)}")
+    direct = out is None or (out.is_cuda and out.is_contiguous())
+    if dir_tile is None:
+        dir_tile = K if direct else max(1, _TILE_BYTES // max(1, 12 * R))
+    dir_tile = max(1, min(int(dir_tile), K))
+    if out is None:
+        out = torch.empty((K, R, 3), dtype=torch.float32, device=dev)
+    brdf = torch.empty((K, R, 3), dtype=torch.float32, device=dev) if want_brdf else None
+    if R > 0:
+        for k0 in range(0, K, dir_tile):
+            k1 = min(K, k0 + dir_tile)
+            rgb_t, _ = Fn.ray_shade_dirs(desc, surface.acc, surface.wsum, surface.rays_d, sun[k0:k1],
+                                         None if view is None else view[k0:k1], rgb=out[k0:k1] if direct else None,
+                                         brdf=None if brdf is None else brdf[k0:k1])
+            if not direct:
+                out[k0:k1].copy_(rgb_t)
+    return (out, brdf) if want_brdf else out
+
+
+@torch.no_grad()
+def relight_image(models, args, rays, sun_dirs, ts=None, chunk=None, apply_brdf=False, apply_theta=False, cos_irra_on=False,
+                  group=None, out=None, return_surface=False, **kw):
+    """render_surface + relight: one geometry pass over the rays of a view, then K ray-level shadings.
+    -> dict rgb (K, R, 3), depth (R,) (+ surface with return_surface).  Replaces K calls of render_image with the sun replaced."""
+    surface = render_surface(models, args, rays, ts=ts, chunk=chunk, apply_brdf=apply_brdf, apply_theta=apply_theta, group=group,
+                             **kw)
+    res = {"rgb": relight(surface, sun_dirs, apply_brdf=apply_brdf, cos_irra_on=cos_irra_on, out=out), "depth": surface.depth}
+    if return_surface:
+        res["surface"] = surface
+    return res
+
+
+@torch.no_grad()
+def brdf_lobe(surface, rows, view_dirs, sun_dirs, apply_brdf=None, cos_irra_on=False):
+    """The BRDF of the chosen pixels over a grid of view directions (eval.py's eval_pixel_variedvw): -> (brdf, rgb), each
+    (len(rows), V, 3); brdf is the value before irradiance and clamp, which is what a lobe plot shows.  sun_dirs: one fixed sun
+    (3,) / (1, 3), or (V, 3) paired with view_dirs.  No field evaluation: the pixel's composited normal, albedo and BRDF
+    parameters stay as rendered.  With --input_viewdir the field's own view input stays the camera's (the albedo head was
+    evaluated for the rendered ray); only the BRDF's view direction varies."""
+    sub = surface.select(rows)
+    rgb, brdf = relight(sub, sun_dirs, apply_brdf=apply_brdf, cos_irra_on=cos_irra_on, view_dirs=view_dirs, want_brdf=True)
+    return brdf.permute(1, 0, 2).contiguous(), rgb.permute(1, 0, 2).contiguous()
+
+
+__all__ = ["Surface", "render_surface", "relight", "relight_image", "brdf_lobe", "directions"]

@@ -7,6 +7,8 @@ torch.randn (R,S+G)), so a harness that monkeypatches torch.rand/rand_like/randn
 reference's draws.  Documented differences: the reference's print/`check_nan` host syncs are not
 reproduced; pass 1 runs without autograd (its result is detached upstream, rendering.py:262).
 """
+from types import SimpleNamespace
+
 import torch
 
 from . import functions as Fn
@@ -291,10 +293,11 @@ def shade_desc(model, args, spec, apply_brdf, cos_irra_on, lambda_rgb=1.0, lambd
     return d
 
 
-def render_rays(models, args, rays, ts, mode="test", valid_depth=None, target_depths=None, target_std=None,
-                apply_brdf=False, print_debuginfo=False, bTestNormal=False, bTestSun_v=False, gsam_only=False, rows=None,
-                cols=None, percent=0, apply_theta=False, cos_irra_on=False):
-    """render_rays, spsbrdf-nerf branch (rendering.py:168-291)."""
+def _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, target_std, apply_brdf, bTestNormal, bTestSun_v,
+                   gsam_only, apply_theta):
+    """render_rays up to the final compositing: pass 1, the optional sun-visibility pass and the guided samples, with every
+    random draw of the reference in its order.  Shared by render_rays and relight.render_surface (which stops at the composited
+    sums).  -> namespace of the pieces the final pass reads."""
     if args.model != "spsbrdf-nerf":
         raise ValueError("brdf_nerf_amd.render_rays serves --model spsbrdf-nerf only")
     if args.n_importance > 0:
@@ -374,16 +377,35 @@ def render_rays(models, args, rays, ts, mode="test", valid_depth=None, target_de
         # the clamp window is the FIRST ray's (near, far) (rendering.py:133,144): read by the kernel from rays[0, 6:8]
         z2, z_all, idx = Fn.guided_samples(z_vals, w1, d1, u, rays[0, 6:8], None, args.std_range, use_t, tdep,
                                            tstd, u_t, trow, merge=not gsam_only)
+    return SimpleNamespace(model=model, spec=spec, packed=packed, rays=rays, rays_d=rays_d, sun_d=sun_d, rays_t=rays_t, z_vals=z_vals,
+                           out1=out1, sun_res=sun_res, z2=z2, z_all=z_all, idx=idx)
+
+
+def _composite_merged(p, args):
+    """The final pass of the merged sample set (rendering.py:263-272): the guided samples' field evaluation, the depth-sorted
+    union and its compositing.  -> out (R, S+G, C), alphas, transparency, weights, depth, acc."""
+    R, G = p.z2.shape
+    C = p.spec.out_channels
+    out2 = p.model.evaluate(p.spec, p.packed, rays=p.rays, z=p.z2, t_embed=p.rays_t).view(R, G, C)
+    out = torch.cat([p.out1, out2], 1).gather(1, p.idx.unsqueeze(-1).expand(-1, -1, C))      # depth-sorted order
+    noise2 = torch.randn(R, p.z_all.shape[1], device=p.rays.device)
+    return (out,) + tuple(Fn.composite(p.z_all, out, noise2 if args.noise_std != 0 else None, args.noise_std))
+
+
+def render_rays(models, args, rays, ts, mode="test", valid_depth=None, target_depths=None, target_std=None,
+                apply_brdf=False, print_debuginfo=False, bTestNormal=False, bTestSun_v=False, gsam_only=False, rows=None,
+                cols=None, percent=0, apply_theta=False, cos_irra_on=False):
+    """render_rays, spsbrdf-nerf branch (rendering.py:168-291)."""
+    p = _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, target_std, apply_brdf, bTestNormal, bTestSun_v,
+                       gsam_only, apply_theta)
+    model, spec = p.model, p.spec
     if gsam_only:
-        result, brdf_type = inference(model, args, None, z2, rays_d=rays_d, sun_d=sun_d, rays_t=rays_t, z_vals_unsort=z2, apply_brdf=apply_brdf,
-                                      bTestNormal=bTestNormal, sun_res=sun_res, sort_idx=None, mode=mode, apply_theta=apply_theta,
-                                      cos_irra_on=cos_irra_on, _rays=rays, _packed=packed, rows=rows, cols=cols)
+        result, brdf_type = inference(model, args, None, p.z2, rays_d=p.rays_d, sun_d=p.sun_d, rays_t=p.rays_t, z_vals_unsort=p.z2,
+                                      apply_brdf=apply_brdf, bTestNormal=bTestNormal, sun_res=p.sun_res, sort_idx=None, mode=mode,
+                                      apply_theta=apply_theta, cos_irra_on=cos_irra_on, _rays=p.rays, _packed=p.packed, rows=rows, cols=cols)
         return {f"{k}_coarse": v for k, v in result.items()}, brdf_type
-    z_unsort = torch.cat([z_vals, z2], -1)
-    out2 = model.evaluate(spec, packed, rays=rays, z=z2, t_embed=rays_t).view(R, G, C)
-    out = torch.cat([out1, out2], 1).gather(1, idx.unsqueeze(-1).expand(-1, -1, C))      # depth-sorted order
-    noise2 = torch.randn(R, S + G, device=rays.device)
-    alphas, transparency, weights, depth, acc = Fn.composite(z_all, out, noise2 if noise_on else None, args.noise_std)
-    result, brdf_type = shade(model, args, spec, out, z_all, alphas, transparency, weights, depth, acc, rays_d, sun_d, apply_brdf,
-                              cos_irra_on, idx, z_unsort, rows=rows, cols=cols)
+    z_unsort = torch.cat([p.z_vals, p.z2], -1)
+    out, alphas, transparency, weights, depth, acc = _composite_merged(p, args)
+    result, brdf_type = shade(model, args, spec, out, p.z_all, alphas, transparency, weights, depth, acc, p.rays_d, p.sun_d, apply_brdf,
+                              cos_irra_on, p.idx, z_unsort, rows=rows, cols=cols)
     return {f"{k}_coarse": v for k, v in result.items()}, brdf_type

@@ -430,6 +430,18 @@ int bn_ray_shade_loss(const bn_shade_desc *desc, const float *acc, const float *
                       const float *target_weight, int64_t tw_stride, const float *target_std, int64_t ts_stride, int64_t R,
                       float *rgb, float *ray_loss, float *loss_acc, int32_t loss_slots, float *d_acc, float *d_wsum,
                       float *d_depth, unsigned long long *nonfinite, const float *extra_loss, void *stream);
+/* The shading of bn_ray_shade_loss under K directions at once, forward only: relighting a rendered view and the BRDF lobe of a
+ * pixel from ONE geometry pass (acc, wsum do not depend on the sun; replaces create_dsm.py:44-77 and eval.py's
+ * eval_pixel_variedvw, which render again per direction).  desc as above (its loss fields unused; irr must be NULL: a sun-pass
+ * irradiance depends on the sun).  acc [R][C], wsum [R]; rays_d [R] rows with element stride rd_stride; sun [K][3];
+ * view [K][3] nullable: when given it replaces -rays_d for every ray (lobe mode; rays_d may then be NULL).
+ *   brdf[k][r] = BRDF(sun[k], view ? view[k] : -rays_d[r], l2_normalize(acc[r][ch_normal : +3]), albedo_s[r], parameters[r])
+ *   rgb[k][r]  = clamp(irradiance[k] * brdf[k][r], 0, 1),  irradiance = |sun[k].z| with cos_irradiance and a normal channel, else 1
+ * rgb [K][R][3]; brdf [K][R][3] nullable.  kind LAMBERT: the "BRDF" is albedo_s.  With K == 1 and sun = the rays' own sun, rgb is
+ * what bn_ray_shade_loss writes.  Every (direction, ray) is computed on its own: results do not depend on K or on how the
+ * directions are split over calls. */
+int bn_ray_shade_dirs(const bn_shade_desc *desc, const float *acc, const float *wsum, const float *rays_d, int64_t rd_stride,
+                      const float *sun, const float *view, int64_t R, int32_t K, float *rgb, float *brdf, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
