@@ -558,6 +558,12 @@ def _strided(t):
     return C.c_void_p(t.data_ptr()), t.stride(0) if t.shape[0] > 1 else 1
 
 
+def _depth_targets(use, valid_depth, target_depth, target_weight, target_std):
+    """The DepthLoss inputs as the kernels take them: (pointer, stride) of each of the four 1-d views in turn, all null with the
+    term off."""
+    return tuple(a for t in (valid_depth, target_depth, target_weight, target_std) for a in _strided(t if use else None))
+
+
 def composite_guided(z, out1, G, near_far, d_range, use_target=None, target_depth=None, target_std=None, u=None, u_target=None,
                      state=None, bufs=None, want_pass1=False, ray_offset=0, sigma=None, noise=None):
     """Pass-1 compositing of out1 [R][S][C] (sigma = channel 3; or `sigma` [R][S] from a sigma-only pass 1, out1 = None) +
@@ -654,11 +660,7 @@ def ray_shade_loss(desc, acc, wsum, depth, var, rays_d, sun_d, rgbs, bufs=None, 
     b = bufs if bufs is not None else {}
     shapes = dict(rgb=(R, 3), d_acc=(R, Cc), d_wsum=(R,), d_depth=(R,))
     o = {k: (b[k] if k in b else torch.empty(sh, dtype=torch.float32, device=acc.device)) for k, sh in shapes.items()}
-    use = target_depth is not None and desc.lambda_ds > 0
-    vp, vs = _strided(valid_depth if use else None)
-    tdp, tds = _strided(target_depth if use else None)
-    twp, tws = _strided(target_weight if use else None)
-    tsp, tss = _strided(target_std if use else None)
+    dt = _depth_targets(target_depth is not None and desc.lambda_ds > 0, valid_depth, target_depth, target_weight, target_std)
 
     def rows3(t):
         if t is None:
@@ -669,8 +671,8 @@ def ray_shade_loss(desc, acc, wsum, depth, var, rays_d, sun_d, rgbs, bufs=None, 
         return C.c_void_p(t.data_ptr()), t.stride(0)
     rdp, rds = rows3(rays_d)
     sdp, sds = rows3(sun_d)
-    L.check(L.lib().bn_ray_shade_loss(C.byref(desc), _p(acc), _p(wsum), _p(depth), _p(var), rdp, rds, sdp, sds, _p(rgbs), vp, vs, tdp, tds,
-                                      twp, tws, tsp, tss, R, _p(o["rgb"]), _p(ray_loss), _p(loss_acc),
+    L.check(L.lib().bn_ray_shade_loss(C.byref(desc), _p(acc), _p(wsum), _p(depth), _p(var), rdp, rds, sdp, sds, _p(rgbs), *dt, R,
+                                      _p(o["rgb"]), _p(ray_loss), _p(loss_acc),
                                       0 if loss_acc is None else loss_acc.numel(), _p(o["d_acc"]), _p(o["d_wsum"]), _p(o["d_depth"]),
                                       _p(nonfinite), _p(extra_loss), _stream()), "bn_ray_shade_loss")
     return o
@@ -731,12 +733,9 @@ def lambert_tail(z_all, idx, out1, out2, rgbs, rgb_padding, lambda_rgb, d_out1, 
     R, S2 = z_all.shape
     S1, Cc = out1.shape[1], out1.shape[2]
     use = target_depth is not None and lambda_ds > 0
-    vp, vs = _strided(valid_depth if use else None)
-    tdp, tds = _strided(target_depth if use else None)
-    twp, tws = _strided(target_weight if use else None)
-    tsp, tss = _strided(target_std if use else None)
-    L.check(L.lib().bn_lambert_tail(_p(z_all), _p(idx), _p(out1), _p(out2), S1, S2, Cc, R, _p(rgbs), vp, vs, tdp, tds, twp, tws,
-                                    tsp, tss, float(rgb_padding), float(lambda_rgb), float(lambda_ds if use else 0.0),
+    dt = _depth_targets(use, valid_depth, target_depth, target_weight, target_std)
+    L.check(L.lib().bn_lambert_tail(_p(z_all), _p(idx), _p(out1), _p(out2), S1, S2, Cc, R, _p(rgbs), *dt,
+                                    float(rgb_padding), float(lambda_rgb), float(lambda_ds if use else 0.0),
                                     int(bool(usealldepth)), _p(ray_loss), _p(loss_acc), 0 if loss_acc is None else loss_acc.numel(),
                                     _p(rgb), _p(weights), _p(depth),
                                     _p(d_out1), _p(d_out2), _p(nonfinite), _nz(noise), _stream()), "bn_lambert_tail")

@@ -293,6 +293,21 @@ def shade_desc(model, args, spec, apply_brdf, cos_irra_on, lambda_rgb=1.0, lambd
     return d
 
 
+def identity_desc(C, lambda_rgb=1.0, lambda_ds=0.0, lambda_hs=0.0, usealldepth=False):
+    """bn_shade_desc that passes the composited colour through: Lambertian with no padding and no irradiance, the loss lambdas
+    as in shade_desc().  For rows whose colour channels already are the padded, irradiance-weighted BRDF value (one BRDF per
+    sample, bn_sample_brdf_forward); hpk_scl / f0 are fillers this kind never reads."""
+    from . import _lib as L
+    d = L.ShadeDesc()
+    d.kind, d.C, d.ch_normal = L.BN_SHADE_LAMBERT, C, -1
+    d.ch_p0 = d.ch_p1 = d.ch_p2 = -1
+    d.rhoc_is_albedo = d.shell = d.cos_irradiance = 0
+    d.usealldepth = int(bool(usealldepth))
+    d.hpk_scl, d.f0, d.rgb_padding = 1.0, 0.04, 0.0
+    d.lambda_rgb, d.lambda_ds, d.lambda_hs = float(lambda_rgb), float(lambda_ds), float(lambda_hs)
+    return d
+
+
 def _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, target_std, apply_brdf, bTestNormal, bTestSun_v,
                    gsam_only, apply_theta):
     """render_rays up to the final compositing: pass 1, the optional sun-visibility pass and the guided samples, with every

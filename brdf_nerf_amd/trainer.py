@@ -7,7 +7,9 @@ autograd is used only for the per-ray loss glue ((R,3)/(R,) tensors).  Parameter
 nn.Parameters of the drop-in module are views into it, state_dict keys unchanged), so the optimizer and the
 collective are single launches over ~10 MB.
 """
-from collections import OrderedDict
+import functools
+import warnings
+from collections import OrderedDict, namedtuple
 
 import torch
 
@@ -15,7 +17,44 @@ from . import functions as Fn
 from . import _lib as L
 from . import losses
 from .distributed import allreduce_sum_
-from .rendering import shade, shade_desc, get_z_vals, inference, sun_far
+from .rendering import shade, shade_desc, identity_desc, get_z_vals, inference, sun_far
+
+# A run of stored sample rows: field outputs `out` with their activation `stash`, evaluated at depths z (s1 per ray) and - when both
+# passes share the array - behind them at z2 (s2 per ray); rows [row0, row0 + len(out)) of the step's row set
+_Block = namedtuple("_Block", "out stash z z2 s1 s2 row0")
+
+
+class _Rows:
+    """Where a launch-lean step's sample rows live.  The storage layouts - the guided block alone (gsam_only), one array for both
+    passes (merged), one array per pass - differ only in how this record is filled (_lean_body's forward part); the per-sample
+    BRDF launches, the ray tail and the field backward read it and do not ask which layout it is.
+    blocks: the _Block runs in row order; z_all / idx: depths and sort index of the composited set (idx None: rows are in depth
+    order); src: the (R, S1, C) / (R, S2, C) source views the compositing kernels take (second None: one source); d_all: the
+    gradient rows [n][C] the field backward starts from, d_src its views like src."""
+
+    def __init__(self, blocks, z_all, idx, src, d_all):
+        self.blocks, self.z_all, self.idx, self.src, self.d_all = blocks, z_all, idx, src, d_all
+        self.R, self.S1 = src[0].shape[:2]
+        self.S2 = 0 if src[1] is None else src[1].shape[1]
+        self.n = self.R * (self.S1 + self.S2)
+        self.d_src = self.split(d_all)
+
+    def split(self, a):
+        """The (R, S1, c) / (R, S2, c) views of an array [n][c] laid out like the row set."""
+        n1 = self.R * self.S1
+        return a[:n1].view(self.R, self.S1, -1), (a[n1:].view(self.R, self.S2, -1) if self.S2 else None)
+
+    @staticmethod
+    def of(a, block):
+        """The rows of `block` in an array [n][c] laid out like the row set."""
+        return a[block.row0:block.row0 + block.out.shape[0]]
+
+
+def _reg_lambdas(spec, reg):
+    """(hs, nr_an, nr_lr, nr_spv) of a step's regularisers as the kernels take them; NormalLoss (nr_spv_type 1, main.py:297-303)
+    compares the two normal fields, so it is off unless the spec has both."""
+    spv = float(reg.get("nr_spv", 0)) if (spec.normal_an and spec.normal_lr and abs(reg.get("nr_spv", 0)) > 1e-5) else 0.0
+    return float(reg.get("hs", 0)), float(reg.get("nr_an", 0)), float(reg.get("nr_lr", 0)), spv
 
 
 class FusedTrainer:
@@ -52,7 +91,6 @@ class FusedTrainer:
         self.lean = True
         self.merge_passes = True        # one output array / stash / backward for both passes (False: two backward launch sets)
         self.overlap_allreduce = True   # world > 1: all-reduce the trunk's gradient while the rest of the backward still runs
-        self._kind_cache = {}
         self.ray_offset = 0             # index of this rank's first ray in the global batch: in-kernel draws are taken per GLOBAL ray
         self.keep_grads = False         # True: the optimiser launch leaves the step's gradient in flat_grad (tests, diagnostics)
         self.seed_hook = None           # callable(name, tensor): sees / may overwrite "z2" (guided depths), "out_all" (the per-sample field
@@ -206,7 +244,7 @@ class FusedTrainer:
                 sig = Fn.field_sigma(spec, named, packed, rays=rays, z=z).view(R, S)
                 _, _, w1, d1 = Fn.composite(z, sig, noise1, args.noise_std)
             sun_res = None
-            if getattr(model, "sun_v", "none") == "analystic" and apply_brdf:
+            if sun_on:
                 # sun-visibility pass (rendering.py:244-259), detached upstream: sigma only along the sun direction from
                 # the pass-1 surface point; same draws, in the same order, as render_rays
                 if not gsam_only:
@@ -337,22 +375,6 @@ class FusedTrainer:
         return loss.detach(), res["rgb"].detach()
 
     # ------------------------------------------------------------------ launch-lean step
-    def _sample_desc(self, spec, apply_brdf, cos_irra_on):
-        """bn_shade_desc of the per-sample BRDF launches of a MultiBRDF lean step (cached: its fields are launch arguments)."""
-        key = ("sample", spec.key(), bool(apply_brdf), bool(cos_irra_on))
-        d = self._kind_cache.get(key)
-        if d is None:
-            d = self._kind_cache[key] = shade_desc(self.model, self.args, spec, apply_brdf, cos_irra_on)
-        return d
-
-    def _shade_kind(self, spec, apply_brdf, cos_irra_on):
-        """BN_SHADE_* kind of the ray-level shading for this head set (cached: step() asks on every call)."""
-        key = (spec.key(), bool(apply_brdf), bool(cos_irra_on))
-        k = self._kind_cache.get(key)
-        if k is None:
-            k = self._kind_cache[key] = shade_desc(self.model, self.args, spec, apply_brdf, cos_irra_on).kind
-        return k
-
     def _near_far(self, rays, near_far):
         if near_far is None:
             return rays[0, 6:8]
@@ -362,7 +384,17 @@ class FusedTrainer:
             t = self._nf_dev[key] = torch.tensor(key, dtype=torch.float32, device=rays.device)
         return t
 
-    def _sync_state(self, on):
+    def _active_groups(self, apply_brdf, apply_theta):
+        """Which Adam groups (in the order of self.groups) are in this step's graph: torch.optim.Adam would see grad None for the
+        others and skip them."""
+        on = {"base": True, "brdf": bool(apply_brdf), "theta": bool(apply_brdf and apply_theta)}
+        return [on[g] for g, _, _ in self.groups]
+
+    def _adam_counts(self):
+        """The groups' step counters as the device step state holds them (four slots)."""
+        return [self.adam_steps[g] for g, _, _ in self.groups] + [0] * (4 - len(self.groups))
+
+    def _sync_state(self):
         """Host-side hyper-parameters -> device step state, only when they changed (learning-rate decay, a step taken on the
         other path)."""
         _, lr_v, steps_v, _ = Fn.state_views(self.state)
@@ -375,10 +407,10 @@ class FusedTrainer:
         if nz != self._state_noise:
             Fn.set_state_noise(self.state, nz)
             self._state_noise = nz
-        want = [self.adam_steps[g] for g, _, _ in self.groups] + [0] * (4 - len(self.groups))
+        want = self._adam_counts()
         if want != self._state_adam:
             Fn.set_adam_steps(self.state, want, self.betas)
-            self._state_adam = list(want)
+            self._state_adam = want
 
     def _noise_f32(self):
         """--noise_std as the kernels see it (float32): a Python float that underflows float32 is OFF."""
@@ -387,9 +419,7 @@ class FusedTrainer:
 
     def _step_lean(self, spec, rays, rgbs, valid_depth, depths, depth_std, apply_brdf, apply_theta, cos_irra_on, depth_loss_on,
                    near_far, regularisers, gsam_only=False):
-        model, args = self.model, self.args
         reg = self.reg if regularisers else {}
-        lambertian = (len(spec.heads) == 1 and not spec.normal_an and not spec.normal_lr and reg.get("hs", 0) <= 0)
         if not self._grads_clean:          # the general path leaves its gradient in the flat buffer
             self.flat_grad.zero_()
             self._grads_clean = True
@@ -409,88 +439,95 @@ class FusedTrainer:
         valid_depth, depths = stage("valid_depth", valid_depth), stage("depths", depths)
         depth_std = stage("depth_std", depth_std, flat=True)
         nf = self._near_far(rays, near_far)
-        on = {"base": True, "brdf": bool(apply_brdf), "theta": bool(apply_brdf and apply_theta)}
-        active = [on[g] for g, _, _ in self.groups]
-        self._sync_state(on)
+        active = self._active_groups(apply_brdf, apply_theta)
+        self._sync_state()
         slot = self._rng_step % 64
         body = lambda: self._lean_body(spec, rays, rgbs, valid_depth, depths, depth_std, apply_brdf, cos_irra_on, use_ds, nf, reg,
-                                       lambertian, active, gsam_only)
-        res = None
+                                       active, gsam_only)
         if self.use_graph and self.world == 1 and self.seed_hook is None:
-            sig = (spec.key(), rays.shape, rays.data_ptr(), rgbs.data_ptr(), None if valid_depth is None else valid_depth.data_ptr(),
-                   None if depths is None else depths.data_ptr(), None if depth_std is None else depth_std.data_ptr(),
-                   nf.data_ptr(), use_ds, tuple(active), float(self.ds_lambda), float(self.lambda_rgb), bool(self.usealldepth),
-                   L.deterministic(), int(self.ray_offset), bool(self.keep_grads), bool(self.merge_passes), bool(apply_brdf),
-                   bool(cos_irra_on), float(reg.get("hs", 0)), bool(self.sanitize_grads), float(reg.get("nr_an", 0)),
-                   float(reg.get("nr_lr", 0)), bool(gsam_only), self._noise_f32() != 0.0, float(reg.get("nr_spv", 0)),
-                   bool(self.repeatable_loss),
-                   # model switches that change WHICH launches the step consists of (they are attributes, not part of the head set)
-                   str(getattr(model, "sun_v", "none")), bool(model.MultiBRDF), str(args.data),
-                   # and the host-side constants baked into a captured launch's arguments
-                   int(args.n_samples), int(args.guided_samples), float(args.std_range), float(model.rgb_padding),
-                   int(getattr(args, "funcH", 1)), float(getattr(args, "hpk_scl", 1.0)), float(getattr(args, "fresnel_f0", 0.04)),
-                   int(getattr(args, "shell_hapke", 0)), tuple(float(b) for b in self.betas), float(self.eps), float(self.wd))
-            ent = self._graphs.get(sig)
-            if ent is not None:
-                self._graphs.move_to_end(sig)
-                ent[0].replay()
-                res = ent[1]
-            else:
-                n = self._sig_seen.pop(sig, 0) + 1
-                self._sig_seen[sig] = n
-                while len(self._sig_seen) > 256:           # bounded: signatures that never recur (short last batches, changing flags)
-                    self._sig_seen.popitem(last=False)
-                if n > self.graph_after and sig not in self._no_graph:
-                    if len(self._graphs) >= self.max_graphs:     # evict the least recently replayed capture (and its inputs / pool)
-                        self._graphs.popitem(last=False)
-                        if not self._graph_cap_warned:
-                            import warnings
-                            warnings.warn(f"brdf_nerf_amd: more than {self.max_graphs} distinct training-step signatures were captured; the "
-                                          f"least recently used graph is dropped (inputs whose addresses change every step defeat the replay: "
-                                          f"keep batches in fixed buffers, e.g. RayTable.next_batch(out=...))")
-                            self._graph_cap_warned = True
-                    # keep the inputs AND the scratch alive with the graph: their addresses are baked into it (a step of
-                    # another shape must not free what this graph writes on replay: ADVICE r4)
-                    keep = [rays, rgbs, valid_depth, depths, depth_std, nf]
-                    g = torch.cuda.CUDAGraph()
-                    torch.cuda.synchronize()
-                    self._touched = []
-                    try:
-                        with torch.cuda.graph(g):
-                            out = body()
-                    except Exception as e:      # a runtime that cannot capture this step: it stays eager (the capture launched nothing)
-                        import warnings
-                        warnings.warn(f"brdf_nerf_amd: HIP graph capture of the training step failed ({type(e).__name__}: {e}); "
-                                      f"this step signature runs eagerly")
-                        self._no_graph.add(sig)
-                        self._touched = None
-                        torch.cuda.synchronize()
-                    else:
-                        keep += self._touched
-                        self._touched = None
-                        self._graphs[sig] = (g, out, tuple(keep))
-                        g.replay()            # the capture itself does not execute: this is the step
-                        res = out
-        if res is None:
-            res = body()
+            sig = self._graph_signature(spec, rays, rgbs, valid_depth, depths, depth_std, nf, use_ds, active, apply_brdf, cos_irra_on,
+                                        reg, gsam_only)
+            # the inputs stay alive with a captured step: their addresses are baked into it
+            loss, rgb = self._replay_or_capture(sig, body, [rays, rgbs, valid_depth, depths, depth_std, nf])
+        else:
+            loss, rgb = body()
         self._grads_clean = not self.keep_grads
         self._rng_step += 1
         for (gname, _, _), a in zip(self.groups, active):
             if a:
                 self.adam_steps[gname] += 1
-        self._state_adam = [self.adam_steps[g] for g, _, _ in self.groups] + [0] * (4 - len(self.groups))
-        loss, rgb = res
+        self._state_adam = self._adam_counts()
         if loss is None:
             loss = Fn.state_views(self.state)[3][slot]
         return loss.detach(), rgb.detach()
 
-    def _lean_body(self, spec, rays, rgbs, valid_depth, depths, depth_std, apply_brdf, cos_irra_on, use_ds, nf, reg, lambertian,
-                   active, gsam_only=False):
+    def _graph_signature(self, spec, rays, rgbs, valid_depth, depths, depth_std, nf, use_ds, active, apply_brdf, cos_irra_on, reg,
+                         gsam_only):
+        """Everything a captured step bakes in: two steps with equal signatures issue the same launches with the same arguments."""
+        model, args = self.model, self.args
+        return (spec.key(), rays.shape, rays.data_ptr(), rgbs.data_ptr(), None if valid_depth is None else valid_depth.data_ptr(),
+                None if depths is None else depths.data_ptr(), None if depth_std is None else depth_std.data_ptr(),
+                nf.data_ptr(), use_ds, tuple(active), float(self.ds_lambda), float(self.lambda_rgb), bool(self.usealldepth),
+                L.deterministic(), int(self.ray_offset), bool(self.keep_grads), bool(self.merge_passes), bool(apply_brdf),
+                bool(cos_irra_on), float(reg.get("hs", 0)), bool(self.sanitize_grads), float(reg.get("nr_an", 0)),
+                float(reg.get("nr_lr", 0)), bool(gsam_only), self._noise_f32() != 0.0, float(reg.get("nr_spv", 0)),
+                bool(self.repeatable_loss),
+                # model switches that change WHICH launches the step consists of (they are attributes, not part of the head set)
+                str(getattr(model, "sun_v", "none")), bool(model.MultiBRDF), str(args.data),
+                # and the host-side constants baked into a captured launch's arguments
+                int(args.n_samples), int(args.guided_samples), float(args.std_range), float(model.rgb_padding),
+                int(getattr(args, "funcH", 1)), float(getattr(args, "hpk_scl", 1.0)), float(getattr(args, "fresnel_f0", 0.04)),
+                int(getattr(args, "shell_hapke", 0)), tuple(float(b) for b in self.betas), float(self.eps), float(self.wd))
+
+    def _replay_or_capture(self, sig, body, keep):
+        """The step `body` under signature `sig`: replayed from its captured HIP graph, captured (after graph_after eager steps
+        with this signature; `keep`: the inputs, held with the graph) and replayed, or run eagerly.  -> what body() returns."""
+        ent = self._graphs.get(sig)
+        if ent is not None:
+            self._graphs.move_to_end(sig)
+            ent[0].replay()
+            return ent[1]
+        n = self._sig_seen.pop(sig, 0) + 1
+        self._sig_seen[sig] = n
+        while len(self._sig_seen) > 256:           # bounded: signatures that never recur (short last batches, changing flags)
+            self._sig_seen.popitem(last=False)
+        if n <= self.graph_after or sig in self._no_graph:
+            return body()
+        if len(self._graphs) >= self.max_graphs:     # evict the least recently replayed capture (and its inputs / pool)
+            self._graphs.popitem(last=False)
+            if not self._graph_cap_warned:
+                warnings.warn(f"brdf_nerf_amd: more than {self.max_graphs} distinct training-step signatures were captured; the "
+                              f"least recently used graph is dropped (inputs whose addresses change every step defeat the replay: "
+                              f"keep batches in fixed buffers, e.g. RayTable.next_batch(out=...))")
+                self._graph_cap_warned = True
+        g = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        self._touched = []
+        try:
+            with torch.cuda.graph(g):
+                out = body()
+        except Exception as e:      # a runtime that cannot capture this step: it stays eager (the capture launched nothing)
+            warnings.warn(f"brdf_nerf_amd: HIP graph capture of the training step failed ({type(e).__name__}: {e}); "
+                          f"this step signature runs eagerly")
+            self._no_graph.add(sig)
+            self._touched = None
+            torch.cuda.synchronize()
+            return body()
+        # the scratch stays alive with the graph as well (a step of another shape must not free what this graph writes on
+        # replay: ADVICE r4)
+        self._graphs[sig] = (g, out, tuple(keep + self._touched))
+        self._touched = None
+        g.replay()            # the capture itself does not execute: this is the step
+        return out
+
+    def _lean_body(self, spec, rays, rgbs, valid_depth, depths, depth_std, apply_brdf, cos_irra_on, use_ds, nf, reg, active,
+                   gsam_only=False):
         model, args = self.model, self.args
         S, G = args.n_samples, args.guided_samples
         R, C = rays.shape[0], spec.out_channels
         st = self.state
         named = model.named()
+        sun_on = gsam_only and getattr(model, "sun_v", "none") == "analystic" and apply_brdf
         with torch.no_grad():
             packed = model.repack(spec)                                   # fold + pack: 2 launches
             z = Fn.stratified_z_rng(rays, S, st, self._buf("z", (R, S)), ray_offset=self.ray_offset)
@@ -501,6 +538,7 @@ class FusedTrainer:
             merged = self.merge_passes and (R * S) % tile == 0 and not gsam_only
             n_all = R * (S + G)
             has_t = valid_depth is not None
+            guide = (valid_depth, depths[:, 0], depth_std) if has_t else (None, None, None)
             # --noise_std (models/spsbrdfnerf.py:57-59, multiplied by 0.9 after every step, main.py:246): in-kernel normal draws, one stream for
             # the pass-1 compositing and one for the final compositing of the merged set (the general step draws randn(R, S) and
             # randn(R, S + G) at the same two places)
@@ -512,11 +550,9 @@ class FusedTrainer:
                 # gsam_only stage (main.py:201-203, rendering.py:266-269): pass 1 is a sigma-only forward that only places the
                 # guided samples; the step renders, and back-propagates through, the G guided samples alone
                 sig1 = Fn.field_sigma(spec, named, packed, rays=rays, z=z, out=self._buf("sig1", (R * S,)))
-                sun_on = getattr(model, "sun_v", "none") == "analystic" and apply_brdf
                 if sun_on:
                     bufs = dict(bufs, w1=self._buf("w1", (R, S)), d1=self._buf("d1", (R,)))
-                cg = Fn.composite_guided(z, None, G, nf, args.std_range, valid_depth if has_t else None,
-                                         depths[:, 0] if has_t else None, depth_std if has_t else None, state=st, bufs=bufs,
+                cg = Fn.composite_guided(z, None, G, nf, args.std_range, *guide, state=st, bufs=bufs,
                                          ray_offset=self.ray_offset, sigma=sig1.view(R, S), noise=nz1, want_pass1=sun_on)
                 z2 = cg[0]
                 if sun_on:
@@ -531,29 +567,24 @@ class FusedTrainer:
                     sun_rays = torch.cat([rays[:, 0:3] + rays_d * d1.unsqueeze(-1), sun_d], -1).contiguous()
                     sig_sun = Fn.field_sigma(spec, named, packed, rays=sun_rays, z=z_sun)
                     sun_T = Fn.composite(z_sun, sig_sun.view(R, G), None, 0.0)[1]       # transparency in front of each sample
-                    sun_irr = sun_T[:, -1]
                 if self.seed_hook is not None:
                     self.seed_hook("z2", z2)
                 out2 = self._buf("out2", (R * G, C))
                 stash2 = self._buf("stash2", (Fn.field_stash_bytes(spec, R * G),), torch.uint8)
                 Fn.field_forward_raw(spec, named, packed, out2, stash2, rays=rays, z=z2)
-                # the "merged set" is the guided block alone: no sort index, one source block
-                z_all, idx, out1v, out2v, S = z2, None, out2.view(R, G, C), None, G
-                d_all = self._buf("d_all", (R * G, C))
-                d1o, d2o = d_all.view(R, G, C), None
-            elif merged:
-                out_all = self._buf("out_all", (n_all, C))
-                stash_all = self._buf("stash_all", (Fn.field_stash_bytes(spec, n_all),), torch.uint8)
-                out1, out2 = out_all[:R * S], out_all[R * S:]
-                Fn.field_forward_raw(spec, named, packed, out_all, stash_all, rays=rays, z=z, point_offset=0, total_points=n_all)
+                # the row set is the guided block alone: no sort index, one source block
+                rows = _Rows([_Block(out2, stash2, z2, None, G, 0, 0)], z2, None, (out2.view(R, G, C), None), self._buf("d_all", (R * G, C)))
             else:
-                out1 = self._buf("out1", (R * S, C))
-                stash1 = self._buf("stash1", (Fn.field_stash_bytes(spec, R * S),), torch.uint8)
-                Fn.field_forward_raw(spec, named, packed, out1, stash1, rays=rays, z=z)
-            if not gsam_only:
-                out1v = out1.view(R, S, C)
-                z2, z_all, idx = Fn.composite_guided(z, out1v, G, nf, args.std_range, valid_depth if has_t else None,
-                                                     depths[:, 0] if has_t else None, depth_std if has_t else None, state=st, bufs=bufs,
+                if merged:
+                    out_all = self._buf("out_all", (n_all, C))
+                    stash_all = self._buf("stash_all", (Fn.field_stash_bytes(spec, n_all),), torch.uint8)
+                    out1 = out_all[:R * S]
+                    Fn.field_forward_raw(spec, named, packed, out_all, stash_all, rays=rays, z=z, point_offset=0, total_points=n_all)
+                else:
+                    out1 = self._buf("out1", (R * S, C))
+                    stash1 = self._buf("stash1", (Fn.field_stash_bytes(spec, R * S),), torch.uint8)
+                    Fn.field_forward_raw(spec, named, packed, out1, stash1, rays=rays, z=z)
+                z2, z_all, idx = Fn.composite_guided(z, out1.view(R, S, C), G, nf, args.std_range, *guide, state=st, bufs=bufs,
                                                      ray_offset=self.ray_offset, noise=nz1)
                 if self.seed_hook is not None:   # (and the guided depths pass 2 is evaluated at)
                     self.seed_hook("z2", z2)
@@ -561,165 +592,67 @@ class FusedTrainer:
                     Fn.field_forward_raw(spec, named, packed, out_all, stash_all, rays=rays, z=z2, point_offset=R * S, total_points=n_all)
                     if self.seed_hook is not None:   # (and the per-sample field outputs [R S + R G][C] of both passes: diagnostics)
                         self.seed_hook("out_all", out_all)
+                    out2 = out_all[R * S:]
+                    blocks = [_Block(out_all, stash_all, z, z2, S, G, 0)]
                 else:
                     out2 = self._buf("out2", (R * G, C))
                     stash2 = self._buf("stash2", (Fn.field_stash_bytes(spec, R * G),), torch.uint8)
                     Fn.field_forward_raw(spec, named, packed, out2, stash2, rays=rays, z=z2)
-                out2v = out2.view(R, G, C)
-                d_all = self._buf("d_all", (n_all, C))
-                d1o, d2o = d_all[:R * S].view(R, S, C), d_all[R * S:].view(R, G, C)
-        loss = None
-        kind_id = self._shade_kind(spec, apply_brdf, cos_irra_on)
-        multi = bool(model.MultiBRDF) and apply_brdf
-        sun_rows = gsam_only and getattr(model, "sun_v", "none") == "analystic" and apply_brdf and (multi or kind_id == L.BN_SHADE_LAMBERT)
-        if (multi and kind_id != L.BN_SHADE_LAMBERT) or sun_rows:
-            # One BRDF per sample (or a per-sample irradiance): the BRDF is a pointwise function of a sample's field outputs, so it
-            # is evaluated on the rows as they are STORED (pass-1 block, guided block: the merged set is never materialised) by ONE
-            # launch (csrc/sample_brdf.hip) that writes a copy of the rows with the padded, irradiance-weighted BRDF value in the
-            # place of the albedo; the compositing + loss + composite-backward kernels run on that copy (padding 0: it is inside bp),
-            # and ONE launch turns the copy's gradient rows into those of the field outputs (J^T in forward-mode duals, like
-            # ray_tail.hip).  Rounds 3-4 went through autograd over the per-point BRDF kernels: ~20 glue launches.
-            rgb = self._buf("rgb", (R, 3))
-            det = self.repeatable_loss
-            ray_loss = self._buf("ray_loss", (R,)) if det else None
-            n1 = R * S                                   # rows of the first block (gsam_only: all of them, S = G here)
-            n_rows = n1 if gsam_only else n_all
-            # (with the sun pass: each row's irradiance is the sun ray's transparency at the row's position in its ray, :265-273 -
-            # a constant of the step; the descriptor then carries this step's array)
-            bdesc = (shade_desc(model, args, spec, apply_brdf, cos_irra_on, irr=sun_T.reshape(-1)) if sun_rows
-                     else self._sample_desc(spec, apply_brdf, cos_irra_on))
-            sun_col = 8 if args.data == "sat" else -1
-            hs = float(reg.get("hs", 0))
-            spv = float(reg.get("nr_spv", 0)) if (spec.normal_an and spec.normal_lr and abs(reg.get("nr_spv", 0)) > 1e-5) else 0.0
-            with_reg = hs > 0 or spv != 0.0 or float(reg.get("nr_an", 0)) > 0 or float(reg.get("nr_lr", 0)) > 0
-            # no regulariser: a 4-channel copy [bp, sigma] for the one-launch Lambertian tail; with one: a FULL-width copy for the
-            # generic compositing kernels, which carry NormalRegLoss / NormalLoss / HardSurfaceLoss on the per-sample normals and weights
-            Cb = C if with_reg else 4
-            # the row blocks as (rows, samples per ray of the first / second part, first row): one launch over [pass 1 | guided]
-            # when they share an array, one per pass otherwise
-            if gsam_only:
-                blocks = [(out2, n1, S, 0, 0)]
-            elif merged:
-                blocks = [(out_all, n1, S, G, 0)]
-            else:
-                blocks = [(out1, n1, S, 0, 0), (out2, R * G, G, 0, n1)]
-            with torch.no_grad():
-                Bd = self._buf("B_full" if with_reg else "B_4", (n_rows, Cb))
-                d_B = self._buf("d_Bfull" if with_reg else "d_B", (n_rows, Cb))
-                for Xb, nb1, s1, s2, r0 in blocks:
-                    Fn.sample_brdf(bdesc, Xb, rays, nb1, s1, s2, Bd[r0:r0 + Xb.shape[0]], sun_col=sun_col)
-                B1 = Bd[:n1].view(R, S, Cb)
-                B2 = None if gsam_only else Bd[n1:].view(R, G, Cb)
-                dB1 = d_B[:n1].view(R, S, Cb)
-                dB2 = None if gsam_only else d_B[n1:].view(R, G, Cb)
+                    blocks = [_Block(out1, stash1, z, None, S, 0, 0), _Block(out2, stash2, z2, None, G, 0, R * S)]
+                rows = _Rows(blocks, z_all, idx, (out1.view(R, S, C), out2.view(R, G, C)), self._buf("d_all", (n_all, C)))
+            # the rest of the step reads `rows` alone: which arrays hold the samples is decided above and nowhere else
+            hs, nr_an, nr_lr, spv = regs = _reg_lambdas(spec, reg)
+            lambda_ds = self.ds_lambda if use_ds else 0.0
+            targets = (valid_depth, depths[:, 0], depths[:, 1], depth_std) if use_ds else (None, None, None, None)
+            tail = functools.partial(self._ray_tail, spec, rows, rays, rgbs, targets, lambda_ds, nz2)
+            kdesc = shade_desc(model, args, spec, apply_brdf, cos_irra_on)       # (built per eager step: its inputs may change on a live trainer)
+            multi = bool(model.MultiBRDF) and apply_brdf
+            sun_rows = sun_on and (multi or kdesc.kind == L.BN_SHADE_LAMBERT)
+            if (multi and kdesc.kind != L.BN_SHADE_LAMBERT) or sun_rows:
+                # One BRDF per sample (or a per-sample irradiance): the BRDF is a pointwise function of a sample's field outputs, so it
+                # is evaluated on the rows as they are STORED (pass-1 block, guided block: the merged set is never materialised) by ONE
+                # launch per array (csrc/sample_brdf.hip) that writes a copy of the rows with the padded, irradiance-weighted BRDF value in
+                # the place of the albedo; the ray tail runs on that copy (padding 0: it is inside bp), and ONE launch per array turns
+                # the copy's gradient rows into those of the field outputs (J^T in forward-mode duals, like ray_tail.hip).
+                # (with the sun pass: each row's irradiance is the sun ray's transparency at the row's position in its ray, :265-273 -
+                # a constant of the step; the descriptor then carries this step's array)
+                bdesc = shade_desc(model, args, spec, apply_brdf, cos_irra_on, irr=sun_T.reshape(-1)) if sun_rows else kdesc
+                sun_col = 8 if args.data == "sat" else -1
+                # no regulariser: a 4-channel copy [bp, sigma] for the one-launch Lambertian tail; with one: a FULL-width copy for the
+                # generic compositing kernels, which carry NormalRegLoss / NormalLoss / HardSurfaceLoss on the per-sample normals and weights
+                with_reg = hs > 0 or spv != 0.0 or nr_an > 0 or nr_lr > 0
+                Bd = self._buf("B_full" if with_reg else "B_4", (rows.n, C if with_reg else 4))
+                d_B = self._buf("d_Bfull" if with_reg else "d_B", Bd.shape)
+                for b in rows.blocks:
+                    Fn.sample_brdf(bdesc, b.out, rays, R * b.s1, b.s1, b.s2, rows.of(Bd, b), sun_col=sun_col)
                 if with_reg:
-                    # identity shading of the composited colour: a Lambertian descriptor with no padding and no irradiance (both
-                    # are inside bp already), the losses and regularisers as for one BRDF per ray
-                    from . import _lib as L_
-                    desc = L_.ShadeDesc()
-                    desc.kind, desc.C, desc.ch_normal = L.BN_SHADE_LAMBERT, C, -1
-                    desc.ch_p0 = desc.ch_p1 = desc.ch_p2 = -1
-                    desc.rhoc_is_albedo = desc.shell = desc.cos_irradiance = 0
-                    desc.usealldepth = int(bool(self.usealldepth))
-                    desc.hpk_scl, desc.f0, desc.rgb_padding = 1.0, 0.04, 0.0
-                    desc.lambda_rgb, desc.lambda_ds, desc.lambda_hs = float(self.lambda_rgb), float(self.ds_lambda if use_ds else 0.0), hs
-                    nreg = Fn.normal_reg(rays[:, 3:6], spec.ch_normal_an if spec.normal_an else -1, spec.ch_normal_lr if spec.normal_lr else -1,
-                                         float(reg.get("nr_an", 0)), float(reg.get("nr_lr", 0)), lambda_spv=spv,
-                                         spv_ray=self._buf("spv_ray", (R, 2)) if spv else None, spv_tot=self._buf("spv_tot", (4,)) if spv else None)
-                    o = Fn.merged_composite_forward(z_all, idx, B1, B2,
-                                                    {k: self._buf("m_" + k, sh) for k, sh in (("depth", (R,)), ("acc", (R, C)),
-                                                                                              ("wsum", (R,)), ("var", (R,)), ("reg", (R,)))},
-                                                    want=("depth", "acc", "wsum", "var"), nreg=nreg, noise=nz2)
-                    sb = {k: self._buf("s_" + k, sh) for k, sh in (("rgb", (R, 3)), ("d_acc", (R, C)), ("d_wsum", (R,)), ("d_depth", (R,)))}
-                    gq = Fn.ray_shade_loss(desc, o["acc"], o["wsum"], o["depth"], o["var"], rays[:, 3:6], None, rgbs, sb,
-                                           valid_depth if use_ds else None, depths[:, 0] if use_ds else None,
-                                           depths[:, 1] if use_ds else None, depth_std if use_ds else None, ray_loss=ray_loss,
-                                           loss_acc=None if det else Fn.state_loss_partials(st),
-                                           nonfinite=self._nonfinite if self.sanitize_grads else None, extra_loss=o.get("reg"))
-                    rgb = gq["rgb"]
-                    if spv:
-                        Fn.normal_spv_reduce(nreg, R, z_all.shape[1], ray_loss=ray_loss, loss_acc=None if det else Fn.state_loss_partials(st))
-                    Fn.merged_composite_backward(z_all, idx, B1, B2, None, gq["d_depth"], gq["d_acc"], dB1, dB2, d_wsum=gq["d_wsum"],
-                                                 nonfinite=self._nonfinite if self.sanitize_grads else None,
-                                                 hs_scale=hs / R if hs > 0 else 0.0, depth=o["depth"], nreg=nreg, noise=nz2)
+                    # identity shading of the composited colour, the losses and regularisers as for one BRDF per ray
+                    loss, rgb = tail(rows.split(Bd), rows.split(d_B), regs=regs,
+                                     desc=identity_desc(C, self.lambda_rgb, lambda_ds, hs, self.usealldepth))
                 else:
-                    Fn.lambert_tail(z_all, idx, B1, B2, rgbs, 0.0, self.lambda_rgb, dB1, dB2,
-                                    valid_depth if use_ds else None, depths[:, 0] if use_ds else None, depths[:, 1] if use_ds else None,
-                                    depth_std if use_ds else None, self.ds_lambda if use_ds else 0.0, self.usealldepth,
-                                    ray_loss=ray_loss, loss_acc=None if det else Fn.state_loss_partials(st), rgb=rgb,
-                                    nonfinite=self._nonfinite if self.sanitize_grads else None, noise=nz2)
-                if det:
-                    loss = ray_loss.sum()
-                for Xb, nb1, s1, s2, r0 in blocks:
-                    Fn.sample_brdf(bdesc, Xb, rays, nb1, s1, s2, d_all[r0:r0 + Xb.shape[0]], backward_of=d_B[r0:r0 + Xb.shape[0]], sun_col=sun_col)
+                    loss, rgb = tail(rows.split(Bd), rows.split(d_B), pad=0.0)
+                for b in rows.blocks:
+                    Fn.sample_brdf(bdesc, b.out, rays, R * b.s1, b.s1, b.s2, rows.of(rows.d_all, b), backward_of=rows.of(d_B, b), sun_col=sun_col)
                 if self.sanitize_grads:
-                    Fn.count_nonfinite(d_all, self._nonfinite)
-                    torch.nan_to_num_(d_all, nan=0.0, posinf=0.0, neginf=0.0)
-        elif lambertian:
-            rgb = self._buf("rgb", (R, 3))
-            det = self.repeatable_loss        # the reported loss too: a fixed-order sum of the per-ray terms instead of atomics
-            ray_loss = self._buf("ray_loss", (R,)) if det else None
-            with torch.no_grad():
-                Fn.lambert_tail(z_all, idx, out1v, out2v, rgbs, model.rgb_padding, self.lambda_rgb, d1o, d2o,
-                                valid_depth if use_ds else None, depths[:, 0] if use_ds else None, depths[:, 1] if use_ds else None,
-                                depth_std if use_ds else None, self.ds_lambda if use_ds else 0.0, self.usealldepth,
-                                ray_loss=ray_loss, loss_acc=None if det else Fn.state_loss_partials(st), rgb=rgb,
-                                nonfinite=self._nonfinite if self.sanitize_grads else None, noise=nz2)
-                if det:
-                    loss = ray_loss.sum()
-        else:
-            # BRDF / normal models: three launches - composited sums of the merged set, the ray-level shading + losses with
-            # their gradients w.r.t. those sums (bn_ray_shade_loss), and the composite backward
-            hs = float(reg.get("hs", 0))
-            desc = shade_desc(model, args, spec, apply_brdf, cos_irra_on, self.lambda_rgb, self.ds_lambda if use_ds else 0.0,
-                              hs, self.usealldepth,
-                              irr=sun_irr if (gsam_only and getattr(model, "sun_v", "none") == "analystic" and apply_brdf) else None)
-            det = self.repeatable_loss
-            ray_loss = self._buf("ray_loss", (R,)) if det else None
-            # NormalRegLoss on the per-sample normals (metrics.py:179-216): its value and gradient come from the compositing kernels
-            # NormalLoss between the two normal fields (nr_spv_type 1, main.py:297-303): two batch-wide means - the rays' sums come
-            # from the forward compositing, a one-workgroup reduce adds them up in fixed order, the backward compositing reads them
-            spv = float(reg.get("nr_spv", 0)) if (spec.normal_an and spec.normal_lr and abs(reg.get("nr_spv", 0)) > 1e-5) else 0.0
-            nreg = Fn.normal_reg(rays[:, 3:6], spec.ch_normal_an if spec.normal_an else -1, spec.ch_normal_lr if spec.normal_lr else -1,
-                                 float(reg.get("nr_an", 0)), float(reg.get("nr_lr", 0)), lambda_spv=spv,
-                                 spv_ray=self._buf("spv_ray", (R, 2)) if spv else None, spv_tot=self._buf("spv_tot", (4,)) if spv else None)
-            with torch.no_grad():
-                o = Fn.merged_composite_forward(z_all, idx, out1v, out2v,
-                                                {k: self._buf("m_" + k, sh) for k, sh in (("depth", (R,)), ("acc", (R, C)),
-                                                                                          ("wsum", (R,)), ("var", (R,)), ("reg", (R,)))},
-                                                want=("depth", "acc", "wsum", "var"), nreg=nreg, noise=nz2)
-                sun_d = rays[:, 8:11] if args.data == "sat" else None
-                sb = {k: self._buf("s_" + k, sh) for k, sh in (("rgb", (R, 3)), ("d_acc", (R, C)), ("d_wsum", (R,)),
-                                                               ("d_depth", (R,)))}
-                g = Fn.ray_shade_loss(desc, o["acc"], o["wsum"], o["depth"], o["var"], rays[:, 3:6], sun_d, rgbs, sb,
-                                      valid_depth if use_ds else None, depths[:, 0] if use_ds else None,
-                                      depths[:, 1] if use_ds else None, depth_std if use_ds else None, ray_loss=ray_loss,
-                                      loss_acc=None if det else Fn.state_loss_partials(st),
-                                      nonfinite=self._nonfinite if self.sanitize_grads else None, extra_loss=o.get("reg"))
-                rgb = g["rgb"]
-                if spv:
-                    Fn.normal_spv_reduce(nreg, R, z_all.shape[1], ray_loss=ray_loss, loss_acc=None if det else Fn.state_loss_partials(st))
-                Fn.merged_composite_backward(z_all, idx, out1v, out2v, None, g["d_depth"], g["d_acc"], d1o, d2o, d_wsum=g["d_wsum"],
-                                             nonfinite=self._nonfinite if self.sanitize_grads else None, hs_scale=hs / R if hs > 0 else 0.0,
-                                             depth=o["depth"], nreg=nreg, noise=nz2)
-                if det:
-                    loss = ray_loss.sum()
+                    Fn.count_nonfinite(rows.d_all, self._nonfinite)
+                    torch.nan_to_num_(rows.d_all, nan=0.0, posinf=0.0, neginf=0.0)
+            elif len(spec.heads) == 1 and not spec.normal_an and not spec.normal_lr and hs <= 0:
+                loss, rgb = tail(rows.src, rows.d_src, pad=model.rgb_padding)
+            else:
+                # BRDF / normal models: one BRDF per ray, evaluated on the composited sums (with the sun pass: under the sun ray's
+                # transparency in front of its LAST sample, spsbrdfnerf.py:354)
+                desc = shade_desc(model, args, spec, apply_brdf, cos_irra_on, self.lambda_rgb, lambda_ds, hs, self.usealldepth,
+                                  irr=sun_T[:, -1] if sun_on else None)
+                loss, rgb = tail(rows.src, rows.d_src, desc=desc, regs=regs, sun_d=rays[:, 8:11] if args.data == "sat" else None)
         if self.seed_hook is not None:       # test hook: sees (and may overwrite) the gradient rows [R (S + G)][C] the field backward starts from
-            self.seed_hook("d_all", d_all)
+            self.seed_hook("d_all", rows.d_all)
         with torch.no_grad():
             def backward(parts, last):
-                """bn_field_backward over the merged set, or over the two passes one after the other; `last`: unfold afterwards."""
-                if gsam_only:
-                    Fn.field_backward_raw(spec, named, self.grad_views, packed, out2, d_all, stash2, rays=rays, z=z2,
-                                          unfold=last, zero_folded=False, parts=parts)
-                elif merged:
-                    Fn.field_backward_raw(spec, named, self.grad_views, packed, out_all, d_all, stash_all, rays=rays, z=z, z2=z2,
-                                          unfold=last, zero_folded=False, parts=parts)
-                else:
-                    Fn.field_backward_raw(spec, named, self.grad_views, packed, out1, d1o.reshape(R * S, C), stash1, rays=rays, z=z,
-                                          unfold=False, parts=parts)
-                    Fn.field_backward_raw(spec, named, self.grad_views, packed, out2, d2o.reshape(R * G, C), stash2, rays=rays, z=z2,
-                                          unfold=last, zero_folded=False, parts=parts)       # (bn_fold_heads clears the folded accumulators)
+                """bn_field_backward over the row blocks one after the other; `last`: unfold afterwards (bn_fold_heads clears the
+                folded accumulators, so nothing is zeroed here)."""
+                for b in rows.blocks:
+                    Fn.field_backward_raw(spec, named, self.grad_views, packed, b.out, rows.of(rows.d_all, b), b.stash, rays=rays, z=b.z,
+                                          z2=b.z2, unfold=last and b is rows.blocks[-1], zero_folded=False, parts=parts)
             if self.world > 1 and self.overlap_allreduce and 0 < self.n_trunk < self.flat_grad.numel():
                 # Two buckets (the reference: DDP's bucketed all-reduce overlapped with backward, main.py:720-731): the trunk's
                 # gradient is final after the trunk weight-gradient launch - its all-reduce (RCCL's own stream, ordered behind
@@ -740,11 +673,49 @@ class FusedTrainer:
                           active, st, self.betas, self.eps, self.wd, 1.0 / self.world, zero_grad=not keep)
         return loss, rgb
 
+    def _ray_tail(self, spec, rows, rays, rgbs, targets, lambda_ds, noise, src, grads, pad=None, desc=None, regs=None, sun_d=None):
+        """Everything between the field forward and the field backward that works on whole rays: compositing of the depth-sorted
+        row set read through `src` (its (R, S1, c) / (R, S2, c) views), shading, the losses and the backward of all of it into the
+        views `grads`.  `pad` (a Lambertian rgb with this padding): ONE launch (bn_lambert_tail).  `desc` + `regs` (a bn_shade_desc,
+        the _reg_lambdas): three - composited sums, the ray-level shading + losses with their gradients w.r.t. those sums
+        (bn_ray_shade_loss), the composite backward - plus the one-workgroup reduce of NormalLoss.
+        targets: DepthLoss's (valid, depth, weight, std) or Nones.  -> (loss or None: it is in the step state's loss ring, rgb)."""
+        R, C = rays.shape[0], spec.out_channels
+        z_all, idx = rows.z_all, rows.idx
+        # the reported loss: a fixed-order sum of the per-ray terms (repeatable_loss), or atomics into the step state's partials
+        ray_loss = self._buf("ray_loss", (R,)) if self.repeatable_loss else None
+        loss_acc = None if self.repeatable_loss else Fn.state_loss_partials(self.state)
+        nonfinite = self._nonfinite if self.sanitize_grads else None
+        if desc is None:
+            rgb = self._buf("rgb", (R, 3))
+            Fn.lambert_tail(z_all, idx, *src, rgbs, pad, self.lambda_rgb, *grads, *targets, lambda_ds, self.usealldepth,
+                            ray_loss=ray_loss, loss_acc=loss_acc, rgb=rgb, nonfinite=nonfinite, noise=noise)
+        else:
+            hs, nr_an, nr_lr, spv = regs
+            # NormalRegLoss on the per-sample normals (metrics.py:179-216): its value and gradient come from the compositing kernels
+            # NormalLoss between the two normal fields (nr_spv_type 1, main.py:297-303): two batch-wide means - the rays' sums come
+            # from the forward compositing, a one-workgroup reduce adds them up in fixed order, the backward compositing reads them
+            nreg = Fn.normal_reg(rays[:, 3:6], spec.ch_normal_an if spec.normal_an else -1, spec.ch_normal_lr if spec.normal_lr else -1,
+                                 nr_an, nr_lr, lambda_spv=spv,
+                                 spv_ray=self._buf("spv_ray", (R, 2)) if spv else None, spv_tot=self._buf("spv_tot", (4,)) if spv else None)
+            o = Fn.merged_composite_forward(z_all, idx, *src,
+                                            {k: self._buf("m_" + k, sh) for k, sh in (("depth", (R,)), ("acc", (R, C)),
+                                                                                      ("wsum", (R,)), ("var", (R,)), ("reg", (R,)))},
+                                            want=("depth", "acc", "wsum", "var"), nreg=nreg, noise=noise)
+            sb = {k: self._buf("s_" + k, sh) for k, sh in (("rgb", (R, 3)), ("d_acc", (R, C)), ("d_wsum", (R,)), ("d_depth", (R,)))}
+            g = Fn.ray_shade_loss(desc, o["acc"], o["wsum"], o["depth"], o["var"], rays[:, 3:6], sun_d, rgbs, sb, *targets,
+                                  ray_loss=ray_loss, loss_acc=loss_acc, nonfinite=nonfinite, extra_loss=o.get("reg"))
+            rgb = g["rgb"]
+            if spv:
+                Fn.normal_spv_reduce(nreg, R, z_all.shape[1], ray_loss=ray_loss, loss_acc=loss_acc)
+            Fn.merged_composite_backward(z_all, idx, *src, None, g["d_depth"], g["d_acc"], *grads, d_wsum=g["d_wsum"],
+                                         nonfinite=nonfinite, hs_scale=hs / R if hs > 0 else 0.0, depth=o["depth"], nreg=nreg, noise=noise)
+        return (ray_loss.sum() if self.repeatable_loss else None), rgb
+
     def _adam(self, apply_brdf, apply_theta=False):
         scale = 1.0 / self.world          # DDP averages gradients
-        on = {"base": True, "brdf": bool(apply_brdf), "theta": bool(apply_brdf and apply_theta)}
-        for gname, lo, hi in self.groups:
-            if not on[gname]:
+        for (gname, lo, hi), on in zip(self.groups, self._active_groups(apply_brdf, apply_theta)):
+            if not on:
                 continue                  # not in this step's graph: torch.optim.Adam would see grad None and skip it
             self.adam_steps[gname] += 1
             Fn.adam_step(self.flat_param[lo:hi], self.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],

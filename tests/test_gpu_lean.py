@@ -804,8 +804,70 @@ def test_lean_step_multibrdf_matches_general_step(name, gsam, cosi, with_reg):
             worst = max(worst, e)
             assert e <= 5e-4, (name, step, e)
         assert len(tb._graphs) >= 1, "the lean step was not captured into a HIP graph"
-        assert any(k[0] == "sample" for k in tb._kind_cache), "the step did not take the per-sample BRDF branch of the lean path"
+        assert any(k[0] in ("B_4", "B_full") for k in tb._bufs), "the step did not take the per-sample BRDF branch of the lean path"
         diag(f"lean step with MultiBRDF {name} gsam_only={gsam} regularisers={with_reg}: worst flat-gradient difference over 4 steps {worst:.2e} of the largest entry")
+    finally:
+        brdf_nerf_amd.set_deterministic(prev)
+
+
+@pytest.mark.parametrize("name,kw,changed", [("hapke_bct", dict(b=1, c=1, theta=1, normal="learned"), dict(hpk_scl=2.5)),
+                                             ("microfacet", dict(roughness=True, normal="analystic"), dict(fresnel_f0=0.11)),
+                                             ("hapke_c_shell", dict(c=1, normal="learned"), dict(shell_hapke=2))])
+def test_lean_step_multibrdf_follows_constants_changed_on_a_live_trainer(name, kw, changed):
+    """The constants a shading descriptor is built from (model.rgb_padding, args.hpk_scl, args.fresnel_f0, args.shell_hapke) are
+    part of the graph signature so that they may change on a live trainer: a --MultiBRDF lean trainer that has already captured
+    its step takes further steps after such a change, against the general step on the same draws (which reads them on every call)
+    - tolerances of test_lean_step_multibrdf_matches_general_step.  hapke_c_shell: a normal field and a Hapke head, no b head, so
+    args.shell_hapke ALONE selects the Hapke shading (rendering.shade() as rendering.shade_desc()): the change turns the KIND, and
+    with it the branch of the lean step, not only scalar fields of the descriptor."""
+    import brdf_nerf_amd
+    from test_gpu_parity import build_model, make_args, Replay
+    from brdf_nerf_amd import functions as Fn
+    from brdf_nerf_amd.trainer import FusedTrainer
+    cfg = FieldConfig(feat=64, n_samples=16, guided_samples=16, MultiBRDF=True, **kw)
+    args = make_args(cfg, "fp32")
+    R, S, G = 96, 16, 16
+    g = torch.Generator().manual_seed(21)
+    rays = _sat_rays(R, g).to(DEV)
+    rgbs = torch.rand(R, 3, generator=g).to(DEV)
+    valid = (torch.rand(R, generator=g) < 0.6).float().to(DEV)
+    depths = torch.stack([0.8 + 0.4 * torch.rand(R, generator=g), torch.rand(R, generator=g)], -1).to(DEV)
+    dstd = (0.03 * torch.rand(R, generator=g)).to(DEV)
+    flags = dict(apply_brdf=True, apply_theta=True, cos_irra_on=False, gsam_only=False)
+    prev = brdf_nerf_amd.set_deterministic(True)
+    try:
+        torch.manual_seed(23)
+        ma, mb = build_model(cfg, 37, "fp32"), build_model(cfg, 37, "fp32")
+        ta = FusedTrainer(ma, args, lr=5e-4, ds_lambda=10.0, strict_rng=False)
+        tb = FusedTrainer(mb, args, lr=5e-4, ds_lambda=10.0, strict_rng=False)
+        ta.lean = False
+        tb.graph_after = 1
+        tb.keep_grads = True
+        for step in range(5):
+            if step == 2:
+                assert len(tb._graphs) == 1, "the lean step was not captured into a HIP graph before the change"
+                ma.rgb_padding = mb.rgb_padding = 0.05
+                for k, v in changed.items():
+                    assert getattr(args, k) != v
+                    setattr(args, k, v)
+            tb.flat_param.copy_(ta.flat_param)
+            tb.exp_avg.copy_(ta.exp_avg)
+            tb.exp_avg_sq.copy_(ta.exp_avg_sq)
+            draws = [Fn.rng_uniform(tb.state, 1, R * S).view(R, S), Fn.rng_uniform(tb.state, 2, R * G).view(R, G),
+                     Fn.rng_uniform(tb.state, 3, R * G).view(R, G)]
+            with Replay(draws) as rp:
+                la, rgb_a = ta.step(rays, rgbs, valid_depth=valid, depths=depths, depth_std=dstd, **flags)
+                assert rp.draws == []
+            lb, rgb_b = tb.step(rays, rgbs, valid_depth=valid, depths=depths, depth_std=dstd, **flags)
+            la, lb = float(la), float(lb)
+            assert la == la, (name, step)
+            assert abs(la - lb) <= 2e-5 * abs(la) + 1e-7, (name, step, la, lb)
+            assert float((rgb_a - rgb_b).abs().max()) <= (1e-4 if name == "microfacet" else 2e-5), (name, step)
+            ga, gb = ta.flat_grad, tb.flat_grad
+            e = float((ga - gb).abs().max()) / float(ga.abs().max())
+            assert e <= 5e-4, (name, step, e)
+        assert len(tb._graphs) == 2, "the step was not captured again under the changed constants"
+        assert any(k[0] == "B_4" for k in tb._bufs), "the step did not take the per-sample BRDF branch of the lean path"
     finally:
         brdf_nerf_amd.set_deterministic(prev)
 
