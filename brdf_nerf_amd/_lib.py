@@ -146,6 +146,8 @@ _SIGS = {
                                     C.c_int64, fptr, C.c_int64, fptr, C.c_int64, C.c_int64, fptr, fptr, fptr, C.c_int32, fptr, fptr,
                                     fptr, fptr, fptr, fptr]),
     "bn_ray_shade_dirs": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int64, fptr, fptr, C.c_int64, C.c_int32, fptr, fptr, fptr]),
+    "bn_sample_shade_dirs": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int64, fptr, fptr, C.c_int64, C.c_int32, C.c_int32, fptr, C.c_int64,
+                                       fptr, C.c_int64, fptr]),
     "bn_lambert_tail": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, fptr, fptr, C.c_int64, fptr,
                                   C.c_int64, fptr, C.c_int64, fptr, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, fptr, fptr,
                                   C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),

@@ -9,6 +9,11 @@
 // output pointers are __restrict__ kernel parameters, see the kernel) and cost no vector registers or vector-memory waits.  The stores
 // to rgb[k][ray][0:3] are contiguous across the lanes of a wave (768 B per direction).  Grid = ray blocks x direction tiles.
 // Replaces eval.py's eval_pixel_variedvw / get_view_dirs loop and create_dsm.py:44-77 (rays[:, 8:11] = sun, render again).
+//
+// With one BRDF per SAMPLE (MultiBRDF == 1; models/spsbrdfnerf.py:289-307, 350-352) the same holds one level down: the colour is
+// sum_s w_s (brdf(row_s, sun, view) (1 + 2 pad) - pad) irr, and neither the depth-sorted rows nor their weights depend on the sun.
+// sample_shade_dirs_kernel (second half of this file) walks a ray's samples once per direction tile and keeps the tile's sums in
+// registers: one geometry pass + R S K pointwise BRDF evaluations instead of K field passes.
 #include "common.h"
 #include "brdfnerf_hip.h"
 #include "prof.h"
@@ -122,6 +127,138 @@ template <int KIND> void launch_masked(int mask, dim3 grid, hipStream_t st, cons
   }
 }
 
+// ------------------------------------------------------------------ one BRDF per sample (MultiBRDF): X [R][S][C], w [R][S]
+struct SampleDirsArgs {
+  bn_shade_desc d;
+  const float *X, *w, *rays_d;
+  int64_t rd_stride;
+  int64_t R, rgb_plane, brdf_plane;
+  int32_t S, K, ktile;
+};
+
+// directions of a tile at most: 6 accumulators each (rgb and brdf sums) stay in registers next to the BRDF body's own
+constexpr int SAMPLE_KT = 8;
+
+// A lane owns a ray.  Outer loop: the ray's samples in ascending s, each row loaded and unpacked ONCE - the raw normal, the raw
+// albedo and the parameter channels, what sample_brdf.hip's row_brdf hands to the same *_eval bodies.  Inner loop: the tile's
+// directions (wave-uniform, through the scalar cache as above).  Every (ray, direction, channel) has one fp32 accumulator that
+// takes its terms in ascending s - no atomics, no cross-lane step - so a result's bits depend on nothing but its own ray and
+// direction: not on the tile, the ray block, K or the caller's chunking.  No sample is skipped: 0 * inf stays the NaN of the
+// reference's sum.
+// The accumulators are indexed by constants only: the direction loop stays ROLLED (one BRDF body per kernel) and rotates the
+// accumulator file by one place per trip - the current direction's sums are always in place 0, and after SAMPLE_KT trips every
+// sum is back where it started.  Trips beyond the tile's n directions (a wave-uniform test) only rotate.
+template <int KIND, int MASK> __global__ __launch_bounds__(64)
+void sample_shade_dirs_kernel(const SampleDirsArgs A, const float *__restrict__ sun, const float *__restrict__ view,
+                              float *__restrict__ rgb_out, float *__restrict__ brdf_out) {
+  const int64_t ray = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (ray >= A.R) return;
+  const bn_shade_desc &q = A.d;
+  const int C = q.C;
+  const float pad = q.rgb_padding, gain = 1.f + 2.f * pad;
+  const bool cosi = q.cos_irradiance && q.ch_normal >= 0;
+  V3<float> vray = {0.f, 0.f, 1.f};
+  if (!view) {
+    const float *rd = A.rays_d + ray * A.rd_stride;
+    vray = {-rd[0], -rd[1], -rd[2]};
+  }
+  const int k0 = (int)blockIdx.y * A.ktile;
+  const int n = min(A.K - k0, A.ktile);                    // 1 <= n <= SAMPLE_KT, the same in every lane
+  float ar[SAMPLE_KT][3], ab[SAMPLE_KT][3];                // sum_s w bp irr ; sum_s w brdf
+#pragma unroll
+  for (int j = 0; j < SAMPLE_KT; ++j)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ar[j][c] = ab[j][c] = 0.f;
+  const float *x = A.X + ray * A.S * C;
+  const float *wr = A.w + ray * A.S;
+  for (int s = 0; s < A.S; ++s, x += C) {
+    const float ws = wr[s];
+    const V3<float> ns = {x[q.ch_normal], x[q.ch_normal + 1], x[q.ch_normal + 2]};
+    float w[3] = {x[0], x[1], x[2]};
+    float p0[3] = {0.f, 0.f, 0.f}, p1[3] = {0.f, 0.f, 0.f}, p2[3] = {0.f, 0.f, 0.f};
+    if (KIND == BN_SHADE_MICROFACET) {
+      p0[0] = x[q.ch_p0];
+    } else {
+      const int n2 = KIND == BN_SHADE_HAPKE ? 1 : 3;          // Hapke's theta is one channel wide
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        if (MASK & 1) p0[c] = x[q.ch_p0 + c];
+        if (MASK & 2) p1[c] = x[q.ch_p1 + c];
+        if ((MASK & 4) && c < n2) p2[c] = (KIND == BN_SHADE_RPV && q.rhoc_is_albedo) ? w[c] : x[q.ch_p2 + c];   // funcH == 2 (:288-291)
+      }
+    }
+#pragma nounroll
+    for (int j = 0; j < SAMPLE_KT; ++j) {
+      float r0 = ar[0][0], r1 = ar[0][1], r2 = ar[0][2], b0 = ab[0][0], b1 = ab[0][1], b2 = ab[0][2];
+      if (j < n) {
+        const float *sk = sun + (int64_t)(k0 + j) * 3;
+        const V3<float> l = {sk[0], sk[1], sk[2]};
+        V3<float> v = vray;
+        if (view) {
+          const float *vk = view + (int64_t)(k0 + j) * 3;
+          v = {vk[0], vk[1], vk[2]};
+        }
+        const float irr = cosi ? fabsf(l.z) : 1.f;           // upward normal: |sun_z| (spsbrdfnerf.py:260-264), else 1
+        float out[3];
+        if (KIND == BN_SHADE_RPV) {
+          rpv_eval<float>(l, v, ns, w, (MASK & 1) ? p0 : nullptr, (MASK & 2) ? p1 : nullptr, (MASK & 4) ? p2 : nullptr, out, nullptr);
+        } else if (KIND == BN_SHADE_HAPKE) {
+          hapke_eval<float>(l, v, ns, w, (MASK & 1) ? p0 : nullptr, (MASK & 2) ? p1 : nullptr, (MASK & 4) ? p2 : nullptr, q.hpk_scl,
+                            q.shell, out, nullptr);
+        } else {
+          microfacet_eval<float>(l, v, ns, w, p0[0], q.f0, out, nullptr);
+        }
+        // (w bp) irr, the reference's order (:350-352); irr == 1 without the cosine term: exact
+        r0 = r0 + ws * (out[0] * gain - pad) * irr;
+        r1 = r1 + ws * (out[1] * gain - pad) * irr;
+        r2 = r2 + ws * (out[2] * gain - pad) * irr;
+        b0 = b0 + ws * out[0];
+        b1 = b1 + ws * out[1];
+        b2 = b2 + ws * out[2];
+      }
+#pragma unroll
+      for (int i = 0; i + 1 < SAMPLE_KT; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          ar[i][c] = ar[i + 1][c];
+          ab[i][c] = ab[i + 1][c];
+        }
+      ar[SAMPLE_KT - 1][0] = r0; ar[SAMPLE_KT - 1][1] = r1; ar[SAMPLE_KT - 1][2] = r2;
+      ab[SAMPLE_KT - 1][0] = b0; ab[SAMPLE_KT - 1][1] = b1; ab[SAMPLE_KT - 1][2] = b2;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < SAMPLE_KT; ++j) {
+    if (j < n) {
+      float *rgb = rgb_out + (int64_t)(k0 + j) * A.rgb_plane + ray * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float v_ = ar[j][c];
+        rgb[c] = isnan(v_) ? v_ : fminf(fmaxf(v_, 0.f), 1.f);
+      }
+      if (brdf_out) {
+        float *b = brdf_out + (int64_t)(k0 + j) * A.brdf_plane + ray * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) b[c] = ab[j][c];
+      }
+    }
+  }
+}
+
+template <int KIND> void launch_sample_masked(int mask, dim3 grid, hipStream_t st, const SampleDirsArgs &a, const float *sun,
+                                              const float *view, float *rgb, float *brdf) {
+  switch (mask) {
+    case 0: sample_shade_dirs_kernel<KIND, 0><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 1: sample_shade_dirs_kernel<KIND, 1><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 2: sample_shade_dirs_kernel<KIND, 2><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 3: sample_shade_dirs_kernel<KIND, 3><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 4: sample_shade_dirs_kernel<KIND, 4><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 5: sample_shade_dirs_kernel<KIND, 5><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    case 6: sample_shade_dirs_kernel<KIND, 6><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+    default: sample_shade_dirs_kernel<KIND, 7><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
+  }
+}
+
 }  // namespace
 
 extern "C" int bn_ray_shade_dirs(const bn_shade_desc *desc, const float *acc, const float *wsum, const float *rays_d,
@@ -166,5 +303,54 @@ extern "C" int bn_ray_shade_dirs(const bn_shade_desc *desc, const float *acc, co
     default: ray_shade_dirs_kernel<BN_SHADE_MICROFACET, 1><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
   }
   BN_LAUNCH_CHECK("ray_shade_dirs");
+  return 0;
+}
+
+extern "C" int bn_sample_shade_dirs(const bn_shade_desc *desc, const float *X, const float *w, const float *rays_d, int64_t rd_stride,
+                                    const float *sun, const float *view, int64_t R, int32_t S, int32_t K, float *rgb, int64_t rgb_plane,
+                                    float *brdf, int64_t brdf_plane, void *stream) {
+  BN_REQUIRE(desc && X && w && sun && rgb && R > 0 && S > 0 && K > 0, "sample_shade_dirs: null argument");
+  const bn_shade_desc &q = *desc;
+  BN_REQUIRE(q.C >= 4 && q.C <= BN_MAX_CH, "sample_shade_dirs: C=%d unsupported", q.C);
+  BN_REQUIRE(q.kind > BN_SHADE_LAMBERT && q.kind <= BN_SHADE_MICROFACET,
+             "sample_shade_dirs: kind=%d (a Lambertian colour is a function of the composited sums: bn_ray_shade_dirs)", q.kind);
+  BN_REQUIRE(!q.irr, "sample_shade_dirs: an irradiance of the sun pass depends on the sun direction (not relightable)");
+  auto in_range = [&](int ch, int n) { return ch < 0 || (ch >= 4 && ch + n <= q.C); };
+  BN_REQUIRE(in_range(q.ch_normal, 3), "sample_shade_dirs: normal channel %d outside [4, %d)", q.ch_normal, q.C);
+  BN_REQUIRE(q.ch_normal >= 4 && (rays_d || view), "sample_shade_dirs: BRDF shading needs a normal field and the ray or view directions");
+  const int n2 = q.kind == BN_SHADE_HAPKE ? 1 : 3;
+  const int n0 = q.kind == BN_SHADE_MICROFACET ? 1 : 3;
+  BN_REQUIRE(in_range(q.ch_p0, n0) && in_range(q.ch_p1, 3) && in_range(q.ch_p2, n2), "sample_shade_dirs: parameter channels (%d, %d, %d) outside [4, %d)",
+             q.ch_p0, q.ch_p1, q.ch_p2, q.C);
+  BN_REQUIRE(q.kind != BN_SHADE_MICROFACET || q.ch_p0 >= 4, "sample_shade_dirs: microfacet needs the roughness channel");
+  BN_REQUIRE(q.kind != BN_SHADE_HAPKE || q.ch_p0 >= 4 || (q.shell >= 1 && q.shell <= 3), "sample_shade_dirs: Hapke without b needs shell_hapke in {1,2,3}");
+  BN_REQUIRE(R <= (int64_t)64 * 0x7fffffff, "sample_shade_dirs: R=%lld too large", (long long)R);
+  BN_REQUIRE(rgb_plane >= R * 3 && (!brdf || brdf_plane >= R * 3), "sample_shade_dirs: planes (%lld, %lld) shorter than R * 3 = %lld",
+             (long long)rgb_plane, (long long)brdf_plane, (long long)(R * 3));
+  SampleDirsArgs a;
+  a.d = q; a.X = X; a.w = w; a.rays_d = rays_d; a.rd_stride = rd_stride; a.R = R; a.rgb_plane = rgb_plane; a.brdf_plane = brdf_plane;
+  a.S = S;
+  // Direction tile: as long as the accumulators allow while ray blocks x tiles still fill the CUs (the rows of a ray are read
+  // once per tile).  Every (direction, ray) is summed on its own: the tiling changes no bit.
+  const int64_t blocks = ceil_div64(R, 64);
+  int64_t kt = (int64_t)K * blocks / 2048;
+  kt = kt < 1 ? 1 : (kt > SAMPLE_KT ? SAMPLE_KT : kt);
+  a.ktile = (int32_t)kt;
+  hipStream_t st = (hipStream_t)stream;
+  BnProfScope prof_(BN_K_BRDF, st);
+  const int mask = (q.ch_p0 >= 0 ? 1 : 0) | (q.ch_p1 >= 0 ? 2 : 0) | ((q.ch_p2 >= 0 || (q.kind == BN_SHADE_RPV && q.rhoc_is_albedo)) ? 4 : 0);
+  const int64_t per_launch = 65535 * kt;                   // gridDim.y <= 65535: more directions take more launches
+  for (int64_t kb = 0; kb < K; kb += per_launch) {
+    a.K = (int32_t)(K - kb < per_launch ? K - kb : per_launch);
+    const dim3 grid((unsigned)blocks, (unsigned)ceil_div64(a.K, kt));
+    const float *sun_b = sun + kb * 3, *view_b = view ? view + kb * 3 : nullptr;
+    float *rgb_b = rgb + kb * rgb_plane, *brdf_b = brdf ? brdf + kb * brdf_plane : nullptr;
+    switch (q.kind) {
+      case BN_SHADE_RPV: launch_sample_masked<BN_SHADE_RPV>(mask, grid, st, a, sun_b, view_b, rgb_b, brdf_b); break;
+      case BN_SHADE_HAPKE: launch_sample_masked<BN_SHADE_HAPKE>(mask, grid, st, a, sun_b, view_b, rgb_b, brdf_b); break;
+      default: sample_shade_dirs_kernel<BN_SHADE_MICROFACET, 1><<<grid, 64, 0, st>>>(a, sun_b, view_b, rgb_b, brdf_b); break;
+    }
+  }
+  BN_LAUNCH_CHECK("sample_shade_dirs");
   return 0;
 }

@@ -704,6 +704,42 @@ def ray_shade_dirs(desc, acc, wsum, rays_d, sun, view=None, rgb=None, brdf=None,
     return rgb, brdf
 
 
+def sample_shade_dirs(desc, X, w, rays_d, sun, view=None, rgb=None, brdf=None, want_brdf=False):
+    """ray_shade_dirs for one BRDF per sample (bn_sample_shade_dirs), forward only.  X (R,S,C) depth-sorted field-output rows,
+    w (R,S) their weights; rays_d (R,3) view with unit inner stride; sun (K,3); view (K,3) or None (-rays_d).  rgb / brdf: (K,R,3)
+    float32 on the device, rows contiguous - the planes may be further apart (a (K, i:j, 3) slice of a whole view).
+    -> rgb (K,R,3) and brdf (K,R,3) = sum_s w brdf_s or None (with `brdf` given or want_brdf)."""
+    R, S, Cc = X.shape
+    K = sun.shape[0]
+    for t in (X, w, sun) + (() if view is None else (view,)):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    assert w.shape == (R, S) and sun.shape == (K, 3) and (view is None or view.shape == (K, 3)) and desc.C == Cc
+    rdp, rds = None, 0
+    if rays_d is not None:
+        assert rays_d.is_cuda and rays_d.dtype == torch.float32 and rays_d.shape == (R, 3)
+        if rays_d.stride(1) != 1:
+            rays_d = rays_d.contiguous()
+        rdp, rds = C.c_void_p(rays_d.data_ptr()), rays_d.stride(0)
+    if rgb is None:
+        rgb = torch.empty((K, R, 3), dtype=torch.float32, device=X.device)
+    if brdf is None and want_brdf:
+        brdf = torch.empty((K, R, 3), dtype=torch.float32, device=X.device)
+    planes = []
+    for t in (rgb, brdf):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.shape == (K, R, 3) and plane_rows(t))
+        planes.append(3 * R if (t is None or K == 1) else t.stride(0))
+    raw = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    L.check(L.lib().bn_sample_shade_dirs(C.byref(desc), _p(X), _p(w), rdp, rds, _p(sun), _p(view), R, S, K, raw(rgb), planes[0],
+                                         raw(brdf), planes[1], _stream()), "bn_sample_shade_dirs")
+    return rgb, brdf
+
+
+def plane_rows(t):
+    """(K,R,3) whose (R,3) planes are contiguous rows and do not overlap: what bn_sample_shade_dirs writes through a plane stride."""
+    K, R, _ = t.shape
+    return R == 0 or ((t.stride(2) == 1 and (R == 1 or t.stride(1) == 3)) and (K == 1 or t.stride(0) >= 3 * R))
+
+
 def sample_brdf(desc, X, rays, n1, S1, S2, out, backward_of=None, sun_col=8):
     """Per-sample BRDF of --MultiBRDF on stored field-output rows (bn_sample_brdf_forward / _backward).  X (N, C) rows of which the
     first n1 are S1 per ray and the rest S2 per ray; rays (R, >= 6) fp32 rows (sun at sun_col, < 0: ones).  Forward: `out` (N, 4) or

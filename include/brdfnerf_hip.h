@@ -442,6 +442,20 @@ int bn_ray_shade_loss(const bn_shade_desc *desc, const float *acc, const float *
  * directions are split over calls. */
 int bn_ray_shade_dirs(const bn_shade_desc *desc, const float *acc, const float *wsum, const float *rays_d, int64_t rd_stride,
                       const float *sun, const float *view, int64_t R, int32_t K, float *rgb, float *brdf, void *stream);
+/* bn_ray_shade_dirs one level down, for a model with one BRDF per SAMPLE (--MultiBRDF 1, models/spsbrdfnerf.py:289-307, 350-352),
+ * forward only: K directions from the depth-sorted field-output rows X [R][S][C] and compositing weights w [R][S] of ONE geometry
+ * pass (neither depends on the sun; replaces K calls of render_rays with rays[:, 8:11] = sun, create_dsm.py:44-77, and eval.py's
+ * eval_pixel_variedvw for such a model).  desc, rays_d, sun, view as in bn_ray_shade_dirs; a sample's BRDF reads the row's raw
+ * normal, raw albedo (channels 0-2) and parameter channels, exactly as bn_sample_brdf_forward does.
+ *   brdf[k][r] = sum_s w[r][s] BRDF(sun[k], view ? view[k] : -rays_d[r], X[r][s])
+ *   rgb[k][r]  = clamp(sum_s w[r][s] (BRDF(...) (1 + 2 pad) - pad) irradiance[k], 0, 1)
+ * written at rgb[k * rgb_plane + r * 3 + c] (rgb_plane >= 3 R: a caller that shades a view chunk by chunk passes the plane of the
+ * whole view) and brdf[k * brdf_plane + r * 3 + c] (nullable).  The sums run over ascending s in fp32, one accumulator per (ray,
+ * direction, channel), and no sample is skipped (0 * inf stays NaN): results do not depend on K, on how directions or rays are
+ * split over calls, or on the kernel's tiling.  kind LAMBERT is refused: that colour is bn_ray_shade_dirs of the composited sums. */
+int bn_sample_shade_dirs(const bn_shade_desc *desc, const float *X, const float *w, const float *rays_d, int64_t rd_stride,
+                         const float *sun, const float *view, int64_t R, int32_t S, int32_t K, float *rgb, int64_t rgb_plane,
+                         float *brdf, int64_t brdf_plane, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
