@@ -17,6 +17,7 @@ DTYPES = {"fp32": BN_F32, "bf16": BN_BF16, "fp16": BN_F16}
 BN_ACT_SIN, BN_ACT_RELU = 0, 1
 BN_HEAD_PLAIN, BN_HEAD_RPV_K, BN_HEAD_RPV_THETA, BN_HEAD_HAPKE_THETA, BN_HEAD_TILE3, BN_HEAD_BETA = 0, 1, 2, 3, 4, 5
 BN_BRDF_AUX = 16
+BN_MAX_G = 256
 
 fptr = C.c_void_p
 
@@ -148,6 +149,9 @@ _SIGS = {
     "bn_ray_shade_dirs": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int64, fptr, fptr, C.c_int64, C.c_int32, fptr, fptr, fptr]),
     "bn_sample_shade_dirs": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int64, fptr, fptr, C.c_int64, C.c_int32, C.c_int32, fptr, C.c_int64,
                                        fptr, C.c_int64, fptr]),
+    "bn_sun_ray_table": (C.c_int, [fptr, C.c_int64, fptr, fptr, fptr, C.c_int64, C.c_int32, C.c_int32, fptr, fptr, fptr]),
+    "bn_sun_shade_dirs": (C.c_int, [fptr, fptr, fptr, fptr, C.c_float, fptr, fptr, fptr, fptr, fptr, C.c_int64, fptr, C.c_int64, C.c_int32,
+                                    C.c_int32, fptr, C.c_int64, fptr, C.c_int64, fptr]),
     "bn_lambert_tail": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, fptr, fptr, C.c_int64, fptr,
                                   C.c_int64, fptr, C.c_int64, fptr, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, fptr, fptr,
                                   C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),

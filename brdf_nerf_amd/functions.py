@@ -740,6 +740,63 @@ def plane_rows(t):
     return R == 0 or ((t.stride(2) == 1 and (R == 1 or t.stride(1) == 3)) and (K == 1 or t.stride(0) >= 3 * R))
 
 
+def sun_ray_table(rays, d1, sun, u, table=None, z_sun=None):
+    """Rays and depths of the sun-visibility pass for K directions in one launch (bn_sun_ray_table).  rays (R, >= 6) float32
+    contiguous, d1 (R,) the pass-1 depth, sun (K, 3), u (R, G) the pass's uniforms, shared by all K.  -> table (K R, 8) rows
+    (surface point, sun_k, 0.01 far, far) and z_sun (K R, G): what field_sigma(rays=table, z=z_sun) takes; per direction bitwise
+    rendering.sun_far + stratified_z + the torch.cat of rendering._sample_passes."""
+    R, G = u.shape
+    K = sun.shape[0]
+    for t in (rays, d1, sun, u):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    assert rays.dim() == 2 and rays.shape[0] == R and rays.shape[1] >= 6 and d1.numel() == R and sun.shape == (K, 3)
+    if table is None:
+        table = torch.empty((K * R, 8), dtype=torch.float32, device=u.device)
+    if z_sun is None:
+        z_sun = torch.empty((K * R, G), dtype=torch.float32, device=u.device)
+    assert table.shape == (K * R, 8) and z_sun.shape == (K * R, G)
+    L.check(L.lib().bn_sun_ray_table(_p(rays), rays.shape[1], _p(d1), _p(sun), _p(u), R, K, G, _p(table), _p(z_sun), _stream()),
+            "bn_sun_ray_table")
+    return table, z_sun
+
+
+def sun_shade_dirs(desc, sigma_sun, z_sun, rays_d, sun, acc=None, wsum=None, X=None, w=None, noise=None, noise_std=0.0, rgb=None,
+                   vis=None, want_vis=False):
+    """Transmittance of the sun pass and the shading that reads it, K directions in one launch (bn_sun_shade_dirs), forward only.
+    sigma_sun, z_sun (K, R, G) (any shape of K R G elements in that order); noise (R, G) or None; either acc (R, C), wsum (R,) - one
+    BRDF per ray - or X (R, G, C), w (R, G) - per-sample shading; rays_d (R, 3) view with unit inner stride; sun (K, 3).  rgb (K, R, 3)
+    / vis (K, R): float32 on the device, rows contiguous - the planes may be further apart (a (K, i:j) slice of a whole view).
+    -> rgb (K, R, 3) and vis (K, R) = T_{G-1} or None (with `vis` given or want_vis)."""
+    K = sun.shape[0]
+    R = (acc if acc is not None else X).shape[0] if (acc is not None or X is not None) else sigma_sun.numel() // max(1, K)
+    G = sigma_sun.numel() // max(1, K * R)
+    dev = sigma_sun.device
+    for t in (sigma_sun, z_sun, sun, acc, wsum, X, w, noise):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous())
+    assert sigma_sun.numel() == K * R * G == z_sun.numel() and sun.shape == (K, 3)
+    assert noise is None or noise.shape == (R, G)
+    assert acc is None or (acc.shape == (R, desc.C) and wsum is not None and wsum.numel() == R)
+    assert X is None or (X.shape == (R, G, desc.C) and w is not None and w.shape == (R, G))
+    rdp, rds = None, 0
+    if rays_d is not None:
+        assert rays_d.is_cuda and rays_d.dtype == torch.float32 and rays_d.shape == (R, 3)
+        if rays_d.stride(1) != 1:
+            rays_d = rays_d.contiguous()
+        rdp, rds = C.c_void_p(rays_d.data_ptr()), rays_d.stride(0)
+    if rgb is None:
+        rgb = torch.empty((K, R, 3), dtype=torch.float32, device=dev)
+    if vis is None and want_vis:
+        vis = torch.empty((K, R), dtype=torch.float32, device=dev)
+    assert rgb.is_cuda and rgb.dtype == torch.float32 and rgb.shape == (K, R, 3) and plane_rows(rgb)
+    assert vis is None or (vis.is_cuda and vis.dtype == torch.float32 and vis.shape == (K, R) and (R == 1 or vis.stride(1) == 1)
+                           and (K == 1 or vis.stride(0) >= R))
+    raw = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    L.check(L.lib().bn_sun_shade_dirs(C.byref(desc), _p(sigma_sun), _p(z_sun), _p(noise), float(noise_std), _p(acc), _p(wsum), _p(X),
+                                      _p(w), rdp, rds, _p(sun), R, G, K, raw(rgb), 3 * R if K == 1 else rgb.stride(0), raw(vis),
+                                      R if (vis is None or K == 1) else vis.stride(0), _stream()), "bn_sun_shade_dirs")
+    return rgb, vis
+
+
 def sample_brdf(desc, X, rays, n1, S1, S2, out, backward_of=None, sun_col=8):
     """Per-sample BRDF of --MultiBRDF on stored field-output rows (bn_sample_brdf_forward / _backward).  X (N, C) rows of which the
     first n1 are S1 per ray and the rest S2 per ray; rays (R, >= 6) fp32 rows (sun at sun_col, < 0: ones).  Forward: `out` (N, 4) or

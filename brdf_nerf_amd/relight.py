@@ -18,7 +18,7 @@ streams) the rows and weights and shades them with bn_sample_shade_dirs: one geo
 is an explicit opt-in because a per-sample surface is S C times larger than the composited one.
 
 Not covered, and refused by name: --MultiBRDF without per_sample=True (shading is per sample), --sun_v analystic (the irradiance
-itself depends on the sun through a field pass), gsam_only.
+itself depends on the sun through a field pass: shadows.py serves that model), gsam_only.
 """
 import torch
 
@@ -48,7 +48,8 @@ def _check_relightable(model, args, gsam_only=False, per_sample=False):
                                   "per_sample=True, which keeps them")
     if getattr(args, "sun_v", "none") == "analystic" or getattr(model, "sun_v", "none") == "analystic":
         raise NotImplementedError("relighting from composited sums does not cover --sun_v analystic: the irradiance is the sun "
-                                  "visibility of a field pass along each sun direction (render_rays per direction)")
+                                  "visibility of a field pass along each sun direction (shadows.relight_image_shadowed runs that "
+                                  "pass per direction on one geometry pass)")
     if gsam_only:
         raise NotImplementedError("relighting does not cover gsam_only=True: the surface is composited from the merged S + G "
                                   "sample set of the default evaluation path")

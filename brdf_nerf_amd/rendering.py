@@ -309,10 +309,12 @@ def identity_desc(C, lambda_rgb=1.0, lambda_ds=0.0, lambda_hs=0.0, usealldepth=F
 
 
 def _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, target_std, apply_brdf, bTestNormal, bTestSun_v,
-                   gsam_only, apply_theta):
+                   gsam_only, apply_theta, defer_sun=False):
     """render_rays up to the final compositing: pass 1, the optional sun-visibility pass and the guided samples, with every
-    random draw of the reference in its order.  Shared by render_rays and relight.render_surface (which stops at the composited
-    sums).  -> namespace of the pieces the final pass reads."""
+    random draw of the reference in its order.  Shared by render_rays, relight.render_surface (which stops at the composited
+    sums) and shadows.render_shadow_surface (defer_sun=True: the sun pass's two draws are taken in their place and kept as
+    sun_draws = (u (R, G), noise (R, G)), the pass itself is left to the caller, who runs it per sun direction).
+    -> namespace of the pieces the final pass reads."""
     if args.model != "spsbrdf-nerf":
         raise ValueError("brdf_nerf_amd.render_rays serves --model spsbrdf-nerf only")
     if args.n_importance > 0:
@@ -360,19 +362,23 @@ def _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, tar
         out1 = model.evaluate(spec, packed, rays=rays, z=z_vals, t_embed=rays_t).view(R, S, C)
         with torch.no_grad():
             _, _, w1, d1, _ = Fn.composite_forward_raw(z_vals, out1.detach(), noise1 if noise_on else None, args.noise_std)
-    sun_res = {}
+    sun_res, sun_draws = {}, None
     if (model.sun_v == "analystic" and apply_brdf) or bTestSun_v:
         # Sun-visibility pass (rendering.py:244-259): transparency along the sun direction from the pass-1 surface
         # point, sigma only, detached.  far_sun is scaled with ROW 0's directions, as upstream (:247-248).
         if not gsam_only:
             raise NotImplementedError("--sun_v analystic needs gsam_only=True: with the merged S+G sample set the reference "
                                       "raises a shape error in pass 2 (SURVEY quirk 2)")
-        with torch.no_grad():
-            far_sun = sun_far(d1, rays_d, sun_d)
-            z_sun = get_z_vals(G, rays.device, far_sun * 0.01, far_sun)
-            sun_rays = torch.cat([rays[:, 0:3] + rays_d * d1.unsqueeze(-1), sun_d], -1).contiguous()
-            rs, _ = inference(model, args, None, z_sun, rays_d=sun_d, mode=mode, sigma_only=True, _rays=sun_rays, _packed=packed)
-        sun_res = {"sun": rs["transparency"].unsqueeze(-1).detach(), "weights_sc": rs["weights"].detach()}
+        if defer_sun:
+            # the draws of get_z_vals(G, ...) and of the sigma-only inference(), in their order
+            sun_draws = (torch.rand_like(d1.unsqueeze(-1).expand(-1, G).contiguous()), torch.randn(R, G, device=rays.device))
+        else:
+            with torch.no_grad():
+                far_sun = sun_far(d1, rays_d, sun_d)
+                z_sun = get_z_vals(G, rays.device, far_sun * 0.01, far_sun)
+                sun_rays = torch.cat([rays[:, 0:3] + rays_d * d1.unsqueeze(-1), sun_d], -1).contiguous()
+                rs, _ = inference(model, args, None, z_sun, rays_d=sun_d, mode=mode, sigma_only=True, _rays=sun_rays, _packed=packed)
+            sun_res = {"sun": rs["transparency"].unsqueeze(-1).detach(), "weights_sc": rs["weights"].detach()}
     # guided samples around the pass-1 depth (or the ground-truth depth prior in training)
     u = torch.rand(R, G, device=rays.device)
     use_t = tdep = tstd = u_t = trow = None
@@ -393,7 +399,7 @@ def _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, tar
         z2, z_all, idx = Fn.guided_samples(z_vals, w1, d1, u, rays[0, 6:8], None, args.std_range, use_t, tdep,
                                            tstd, u_t, trow, merge=not gsam_only)
     return SimpleNamespace(model=model, spec=spec, packed=packed, rays=rays, rays_d=rays_d, sun_d=sun_d, rays_t=rays_t, z_vals=z_vals,
-                           out1=out1, sun_res=sun_res, z2=z2, z_all=z_all, idx=idx)
+                           out1=out1, sun_res=sun_res, z2=z2, z_all=z_all, idx=idx, d1=d1, sun_draws=sun_draws)
 
 
 def _composite_merged(p, args):

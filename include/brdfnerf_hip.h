@@ -456,6 +456,37 @@ int bn_ray_shade_dirs(const bn_shade_desc *desc, const float *acc, const float *
 int bn_sample_shade_dirs(const bn_shade_desc *desc, const float *X, const float *w, const float *rays_d, int64_t rd_stride,
                          const float *sun, const float *view, int64_t R, int32_t S, int32_t K, float *rgb, int64_t rgb_plane,
                          float *brdf, int64_t brdf_plane, void *stream);
+/* Relighting WITH cast shadows (--sun_v analystic; additive to ABI 7): the two ends of the sun-visibility pass (rendering.py:
+ * 244-259) for K sun directions at once; between them bn_field_sigma evaluates the K R G points (rays = table, z = z_sun).
+ *
+ * bn_sun_ray_table: rays and depths of the pass.  rays [R] rows of ray_stride >= 6 floats (origin, direction), d1 [R] the pass-1
+ * depth, sun [K][3], u [R][G] uniforms shared by all K (what K reseeded render_rays calls draw).  Row k R + r of table [K R][8]
+ * is (o_r + d_r d1_r, sun_k, 0.01 far, far) with far = ratio_k d1_r, ratio_k = |rays[0].d_z / sun_k.z| where |sun_k.z| > 1e-5, else 1
+ * - ROW 0 of this call's rays, as upstream (:246-248); z_sun [K R][G] is stratified from (0.01 far, far, u) exactly as
+ * bn_stratified_z does.  Bitwise what rendering.sun_far + bn_stratified_z + the torch.cat of the sun rays give for direction k. */
+#define BN_MAX_G 256             /* guided / sun-pass samples per ray at most */
+int bn_sun_ray_table(const float *rays, int64_t ray_stride, const float *d1, const float *sun, const float *u, int64_t R, int32_t K,
+                     int32_t G, float *table, float *z_sun, void *stream);
+/* bn_sun_shade_dirs: transmittance and shading fused.  sigma_sun, z_sun [K][R][G] (bn_field_sigma's result on the table, and the
+ * table's depths); noise [R][G] nullable, shared by all K, applied as bn_composite_forward applies it (sigma + noise noise_std).
+ *   alpha_s = 1 - exp(-delta_s relu(sigma_s + noise_s noise_std)), delta_s = z_{s+1} - z_s, delta_{G-1} = 1e10
+ *   T_s = prod_{j<s} (1 - alpha_j + 1e-10), multiplied in ascending j                    (models/spsbrdfnerf.py:50-69)
+ * desc as in bn_ray_shade_dirs, with irr NULL.  Exactly one of (acc [R][C], wsum [R]) and (X [R][G][C], w [R][G]) is given:
+ *   per ray    (acc; kind not LAMBERT)  rgb = clamp(T_{G-1} BRDF(sun_k, -rays_d, l2_normalize(acc normal), albedo_s, parameters)):
+ *              the irradiance of the LAST sample (:354) times the BRDF body of bn_ray_shade_dirs
+ *   per sample (X, w)                   rgb = clamp(sum_s w_s (c_s (1 + 2 pad) - pad) T_s), ascending s, one fp32 accumulator per
+ *              channel; c_s the row's albedo for kind LAMBERT (:265-273), else BRDF(row_s, sun_k, -rays_d) as in
+ *              bn_sample_shade_dirs (--MultiBRDF 1, :350-352).  The sun ray's sample index is the view ray's, as upstream.
+ * rgb[k * rgb_plane + r * 3 + c]; vis[k * vis_plane + r] = T_{G-1} (nullable): the shadow map.  Replaces, per direction,
+ * bn_composite_forward on the sun pass (alphas, transparency, weights [R][G] each) and the torch statement of the shading.
+ * Refused: NULL inputs, irr set, cos_irradiance with a normal channel (the cosine branch wins upstream and the sun pass is unused:
+ * bn_ray_shade_dirs / bn_sample_shade_dirs), both or neither of acc / X, per-ray mode with kind LAMBERT, G < 3 or G > BN_MAX_G.
+ * Every (direction, ray) is computed on its own: results do not depend on K, on how directions or rays are split over calls, or on
+ * the kernel's tiling. */
+int bn_sun_shade_dirs(const bn_shade_desc *desc, const float *sigma_sun, const float *z_sun, const float *noise, float noise_std,
+                      const float *acc, const float *wsum, const float *X, const float *w, const float *rays_d, int64_t rd_stride,
+                      const float *sun, int64_t R, int32_t G, int32_t K, float *rgb, int64_t rgb_plane, float *vis, int64_t vis_plane,
+                      void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
