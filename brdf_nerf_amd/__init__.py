@@ -12,8 +12,10 @@ from .rendering import render_rays, inference, get_z_vals, cal_weight  # noqa: F
 from . import functions  # noqa: F401
 from .relight import render_surface, relight, relight_image, brdf_lobe, directions  # noqa: F401
 from .shadows import render_shadow_surface, relight_shadowed, relight_image_shadowed, sun_visibility  # noqa: F401
+from .dsm import SceneFrame, Grid, point_cloud, altitude_image, DsmAccumulator, dsm_image, altitude_mae  # noqa: F401
 from ._lib import set_deterministic  # noqa: F401
 
 __all__ = ["SpSBRDFNeRF", "load_model", "render_rays", "inference", "get_z_vals", "cal_weight", "functions", "set_deterministic",
            "render_surface", "relight", "relight_image", "brdf_lobe", "directions", "render_shadow_surface", "relight_shadowed",
-           "relight_image_shadowed", "sun_visibility"]
+           "relight_image_shadowed", "sun_visibility", "SceneFrame", "Grid", "point_cloud", "altitude_image", "DsmAccumulator",
+           "dsm_image", "altitude_mae"]

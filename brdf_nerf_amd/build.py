@@ -62,7 +62,9 @@ def needs_build():
 # bytes of scratch per lane, the inference forward from 700 to 0 (profiles/history/r03_kernel_resources.txt).
 _NOSLP = ("-fno-slp-vectorize",)
 _TRACKERS = ("-mllvm", "-amdgpu-use-amdgpu-trackers=1") + _NOSLP
-FILE_FLAGS = {"field_wgrad.hip": ("-mllvm", "-amdgpu-sched-strategy=max-ilp"),
+# dsm.hip: the float64 point and cell chain must round operation by operation (a contracted multiply-add moves points across
+# cell boundaries); the file also carries the pragma.
+FILE_FLAGS = {"field_wgrad.hip": ("-mllvm", "-amdgpu-sched-strategy=max-ilp"), "dsm.hip": ("-ffp-contract=off",),
               "field_fwd.hip": _NOSLP,
               "field_bwd.hip": _TRACKERS, "field_adjoint.hip": _TRACKERS, "field_adjbwd.hip": _TRACKERS}
 

@@ -704,6 +704,38 @@ def ray_shade_dirs(desc, acc, wsum, rays_d, sun, view=None, rgb=None, brdf=None,
     return rgb, brdf
 
 
+def dsm_splat(rays, depth, center, rng, xoff, yoff, resolution, radius, footprint, acc, skipped):
+    """The depths of R rays splatted into a DSM accumulator (bn_dsm_splat).  rays (R, >= 6) float32 rows with unit inner stride
+    (origin, direction), depth (R,) float32; center (3 floats) and rng the scene normalisation, (xoff, yoff) the grid's north-west
+    corner; acc (H, W, 2) int64 = (sum, count) and skipped (1,) int64 on the device, accumulated into."""
+    R = rays.shape[0]
+    assert rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] >= 6
+    assert depth.is_cuda and depth.dtype == torch.float32 and depth.shape == (R,)
+    assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] == 2 and acc.is_contiguous()
+    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    if R == 0:
+        return acc
+    if rays.stride(1) != 1:
+        rays = rays.contiguous()
+    c = (C.c_double * 3)(*[float(v) for v in center])
+    H, W = acc.shape[0], acc.shape[1]
+    L.check(L.lib().bn_dsm_splat(C.c_void_p(rays.data_ptr()), rays.stride(0), _p(depth.contiguous()), R, c, float(rng), float(xoff),
+                                 float(yoff), float(resolution), W, H, int(radius), int(footprint), _p(acc), _p(skipped), _stream()),
+            "bn_dsm_splat")
+    return acc
+
+
+def dsm_resolve(acc, want_count=True):
+    """Mean altitude per cell of a DSM accumulator (bn_dsm_resolve): acc (H, W, 2) int64 -> dsm (H, W) float32, NaN where no
+    point fell, and count (H, W) int32 (or None)."""
+    assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] == 2 and acc.is_contiguous()
+    H, W = acc.shape[0], acc.shape[1]
+    dsm = torch.empty((H, W), dtype=torch.float32, device=acc.device)
+    count = torch.empty((H, W), dtype=torch.int32, device=acc.device) if want_count else None
+    L.check(L.lib().bn_dsm_resolve(_p(acc), W, H, _p(dsm), _p(count), _stream()), "bn_dsm_resolve")
+    return dsm, count
+
+
 def sample_shade_dirs(desc, X, w, rays_d, sun, view=None, rgb=None, brdf=None, want_brdf=False):
     """ray_shade_dirs for one BRDF per sample (bn_sample_shade_dirs), forward only.  X (R,S,C) depth-sorted field-output rows,
     w (R,S) their weights; rays_d (R,3) view with unit inner stride; sun (K,3); view (K,3) or None (-rays_d).  rgb / brdf: (K,R,3)

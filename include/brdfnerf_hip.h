@@ -487,6 +487,38 @@ int bn_sun_shade_dirs(const bn_shade_desc *desc, const float *sigma_sun, const f
                       const float *acc, const float *wsum, const float *X, const float *w, const float *rays_d, int64_t rd_stride,
                       const float *sun, int64_t R, int32_t G, int32_t K, float *rgb, int64_t rgb_plane, float *vis, int64_t vis_plane,
                       void *stream);
+/* Digital surface model of a rendered view (additive to ABI 7): the reference's host path - the point cloud of
+ * get_latlonalt_from_nerf_prediction (datasets/satellite_rgb_dep.py:601-634, cs == 'utm': a denormalised point is (east, north,
+ * altitude), :632-633) rasterised by plyflatten(cloud, xoff, yoff, resolution, xsize, ysize, radius=1, sigma=inf) (:636-699) -
+ * as two launches on the device, bitwise reproducible.
+ *
+ * bn_dsm_splat: rays [R] rows of ray_stride >= 6 floats (origin, direction), depth [R]; center (HOST pointer, 3 doubles) and
+ * range are the dataset's normalisation (:622-625); xoff / yoff the grid's western / NORTHERN edge (the affine transform of :695:
+ * row 0 is the northern edge), resolution > 0 the cell size, W x H the grid.  Per ray, in float64 with the fp32 inputs widened
+ * exactly and every operation rounded on its own (no fused multiply-add):
+ *   p = (o + d depth) range + center ;  i = floor((p.x - xoff) / resolution) ;  j = floor((yoff - p.y) / resolution)
+ *   for k1, k2 in [-radius, radius] (footprint BN_DSM_DISC: only k1^2 + k2^2 <= radius^2; BN_DSM_SQUARE: all (2 radius + 1)^2):
+ *     cell (row j + k2, column i + k1), if inside the grid - each cell tested on its own, so a point whose centre cell is outside
+ *     still reaches its neighbours inside - receives  sum += llrint(p.z 2^20), count += 1
+ * acc: int64 [H][W][2] = (sum, count) per cell, 16-byte aligned device memory that the CALLER zeroes; several calls (chunks of a
+ * view, several views) accumulate into it.  Both are integer atomic adds (the sum in two's complement) and there is no float
+ * atomic: acc's bits do not depend on the order of the rays, on how they are split over calls, or on which device splatted
+ * which ray - accumulators of several devices add up (SUM all-reduce) to the single-device one.
+ * A row with a non-finite p or |p.z| >= 2^23 m deposits nothing and adds 1 to skipped[0] (a 64-bit device counter the caller
+ * zeroes).  With that bound |llrint(p.z 2^20)| <= 2^43: a cell holds at least 2^20 points before its sum can overflow.
+ * sigma = inf (the unweighted mean) is the only mode upstream uses and the only one served.  The footprint is the rule stated
+ * HERE; it was not, and could not be, checked against the plyflatten package, which this project does not depend on.
+ * Refused (BN_EINVAL): NULL pointers, radius < 0 or > BN_DSM_MAX_RADIUS, another footprint, resolution <= 0, a non-finite frame
+ * or origin, W H over 2^31 cells, ray_stride < 6.
+ *
+ * bn_dsm_resolve: dsm [H][W] = (float)((double)sum / (double)count 2^-20), NaN where count == 0 - the reference's nodata
+ * (:693); count [H][W] int32 (nullable), saturating at 2^31 - 1. */
+enum { BN_DSM_DISC = 0, BN_DSM_SQUARE = 1 };
+#define BN_DSM_MAX_RADIUS 4
+int bn_dsm_splat(const float *rays, int64_t ray_stride, const float *depth, int64_t R, const double *center, double range, double xoff,
+                 double yoff, double resolution, int32_t W, int32_t H, int32_t radius, int32_t footprint, long long *acc,
+                 unsigned long long *skipped, void *stream);
+int bn_dsm_resolve(const long long *acc, int32_t W, int32_t H, float *dsm, int32_t *count, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
