@@ -62,6 +62,7 @@ class ShadeDesc(C.Structure):         # bn_shade_desc
 BN_SHADE_LAMBERT, BN_SHADE_RPV, BN_SHADE_HAPKE, BN_SHADE_MICROFACET = 0, 1, 2, 3
 BN_DSM_DISC, BN_DSM_SQUARE = 0, 1
 BN_DSM_MAX_RADIUS = 4
+BN_SSIM_MAX_WINDOW = 11
 
 
 class NormalReg(C.Structure):         # bn_normal_reg
@@ -157,6 +158,10 @@ _SIGS = {
     "bn_dsm_splat": (C.c_int, [fptr, C.c_int64, fptr, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_double,
                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, fptr, fptr, fptr]),
     "bn_dsm_resolve": (C.c_int, [fptr, C.c_int32, C.c_int32, fptr, fptr, fptr]),
+    "bn_ssim_map": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, fptr, C.c_double,
+                              C.c_double, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, fptr, fptr, fptr]),
+    "bn_grid_normals": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_double, fptr, fptr]),
+    "bn_normal_angle": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, fptr, C.c_int32, fptr, fptr, fptr]),
     "bn_lambert_tail": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, fptr, fptr, C.c_int64, fptr,
                                   C.c_int64, fptr, C.c_int64, fptr, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, fptr, fptr,
                                   C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),

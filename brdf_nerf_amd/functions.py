@@ -736,6 +736,53 @@ def dsm_resolve(acc, want_count=True):
     return dsm, count
 
 
+def ssim_map(pred, gt, C_, H, W, strides, mask, div, max_val, window, g, sums, rows=None, out=None):
+    """The SSIM index map of two images and its integer sum (bn_ssim_map).  pred, gt: contiguous float32 device buffers read
+    through the element strides (plane, row, col) - no copy; mask (H, W) uint8 or None; g the `window` float64 Gaussian weights;
+    sums (3,) int64 = (sum of llrint(v 2^30), cells summed, cells skipped), accumulated into; rows = (row0, row1) output rows
+    (default all); out (C, H, W) float32 map or None."""
+    sp, sr, sc = (int(s) for s in strides)
+    last = (C_ - 1) * sp + (H - 1) * sr + (W - 1) * sc
+    for t in (pred, gt):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and min(sp, sr, sc) >= 0 and last < t.numel()
+    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == (H, W) and mask.is_contiguous())
+    assert sums.is_cuda and sums.dtype == torch.int64 and sums.numel() == 3 and sums.is_contiguous()
+    assert out is None or (out.is_cuda and out.dtype == torch.float32 and out.shape == (C_, H, W) and out.is_contiguous())
+    assert len(g) == window
+    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+    gw = (C.c_double * window)(*[float(v) for v in g])
+    L.check(L.lib().bn_ssim_map(_p(pred), _p(gt), C_, H, W, sp, sr, sc, _p(mask), float(div), float(max_val), int(window), gw, row0, row1,
+                                _p(out), _p(sums), _stream()), "bn_ssim_map")
+    return sums
+
+
+def grid_normals(z, resolution):
+    """The reference's four-cross-product normals of an altitude grid (bn_grid_normals): z (H, W) float32 -> (H, W, 3) float32,
+    zero on the border.  y grows with the row, as upstream: flat ground gives (0, 0, -1)."""
+    assert z.is_cuda and z.dtype == torch.float32 and z.dim() == 2
+    z = z.contiguous()
+    H, W = z.shape
+    out = torch.empty((H, W, 3), dtype=torch.float32, device=z.device)
+    L.check(L.lib().bn_grid_normals(_p(z), H, W, float(resolution), _p(out), _stream()), "bn_grid_normals")
+    return out
+
+
+def normal_angle(n1, n2, mask=None, border=0, sums=None, want_map=True):
+    """The angle in degrees between two normal grids (bn_normal_angle): n1, n2 (H, W, 3) float32, mask (H, W) uint8 (nonzero:
+    inside) or None -> angle (H, W) float32 (or None), sums (6,) int64 = (sum of llrint(a 2^20), count) over all, inside and
+    outside cells, NaN cells left out.  border 0: the reference's (zero border normals: 90 degrees); 1: the border is NaN."""
+    H, W = n1.shape[0], n1.shape[1]
+    for t in (n1, n2):
+        assert t.is_cuda and t.dtype == torch.float32 and t.shape == (H, W, 3) and t.is_contiguous()
+    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == (H, W) and mask.is_contiguous())
+    if sums is None:
+        sums = torch.zeros((6,), dtype=torch.int64, device=n1.device)
+    assert sums.is_cuda and sums.dtype == torch.int64 and sums.numel() == 6 and sums.is_contiguous()
+    angle = torch.empty((H, W), dtype=torch.float32, device=n1.device) if want_map else None
+    L.check(L.lib().bn_normal_angle(_p(n1), _p(n2), H, W, _p(mask), int(border), _p(angle), _p(sums), _stream()), "bn_normal_angle")
+    return angle, sums
+
+
 def sample_shade_dirs(desc, X, w, rays_d, sun, view=None, rgb=None, brdf=None, want_brdf=False):
     """ray_shade_dirs for one BRDF per sample (bn_sample_shade_dirs), forward only.  X (R,S,C) depth-sorted field-output rows,
     w (R,S) their weights; rays_d (R,3) view with unit inner stride; sun (K,3); view (K,3) or None (-rays_d).  rgb / brdf: (K,R,3)

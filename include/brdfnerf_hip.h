@@ -519,6 +519,49 @@ int bn_dsm_splat(const float *rays, int64_t ray_stride, const float *depth, int6
                  double yoff, double resolution, int32_t W, int32_t H, int32_t radius, int32_t footprint, long long *acc,
                  unsigned long long *skipped, void *stream);
 int bn_dsm_resolve(const long long *acc, int32_t W, int32_t H, float *dsm, int32_t *count, void *stream);
+/* Image and normal metrics of a rendered view (additive to ABI 7): the numbers of the reference's evaluation line (eval.py:467-479)
+ * that neither render_image's PSNR nor the altitude MAE covers, as three launches.  Every float64 operation is rounded on its own
+ * (no fused multiply-add) and every sum is an INTEGER atomic add: the results' bits do not depend on the block order or on how
+ * an image's rows are split over calls or devices (SUM all-reduce of the integers merges ranks).
+ *
+ * bn_ssim_map: replaces metrics.py:327-341 (ssim_ -> kornia 0.5.3 ssim(pred, gt, window, max_val): Gaussian window of sigma 1.5,
+ * reflect padding) and the `* mask.view(1, 1, H, W)` of eval.py:471.  pred, gt: C planes of H x W float32; element (c, r, col) is
+ * at [c plane_stride + r row_stride + col col_stride] of BOTH (eval.py:471's .view(1, 3, H, W) of an (H W, 3) buffer is strides
+ * (H W, W, 1); the true image of that buffer is (1, 3 W, 3)).  mask: uint8 [H][W] or NULL (all ones), multiplied in as a number.
+ * g: `window` normalised 1-D Gaussian weights (HOST pointer; the device computes no exp).  Per output cell, in float64:
+ *   x = ((double)pred (double)mask) / div, y likewise from gt; rows and columns outside the image by 'reflect' without repeating
+ *   the edge (-1 -> 1, H -> H - 2); w[k2][k1] = g[k2] g[k1]; the five moments mu_x, mu_y, E[xx], E[yy], E[xy] start at 0.0 and take
+ *   the taps in row-major order (k2 outer, k1 inner) as s = s + w v, v = x, y, x x, y y, x y rounded before the multiply;
+ *   C1 = (0.01 max_val)^2, C2 = (0.03 max_val)^2; sxx = E[xx] - mu_x mu_x, syy, sxy likewise;
+ *   v = ((2 mu_x mu_y + C1) (2 sxy + C2)) / ((mu_x mu_x + mu_y mu_y + C1) (sxx + syy + C2) + 1e-12)
+ * for the output rows [row0, row1) only (the taps still read the whole image).  map: float32 [C][H][W] (nullable) receives (float)v,
+ * rows outside the range untouched.  sums: int64 [3] the CALLER zeroes, += {sum of llrint(v 2^30), cells in that sum, cells
+ * skipped}; a cell whose v is not finite or |v| >= 4 is skipped.  The SSIM is sums[0] / (sums[1] 2^30).  The rule follows kornia
+ * 0.5.3 as documented; it was not checked against the package, which this project does not depend on.
+ * Refused (BN_EINVAL): NULL pred / gt / g / sums, a window that is even or outside [3, BN_SSIM_MAX_WINDOW], H or W <= window / 2
+ * (too small for the reflect padding), C H W over 2^30 (below it the sum cannot overflow), a negative stride, max_val, div or a
+ * weight that is not finite, rows outside [0, H].
+ *
+ * bn_grid_normals: replaces calc_normal_from_pts3d (sat_utils.py:16-50) on get_pts3d_from_dsm (:175-183), as :251-255 call them.
+ * z: float32 [H][W] altitudes.  Interior cell (r, c): P(r, c) = (c resolution, r resolution, z[r][c]) in float64; the vectors to the
+ * south (r + 1), north (r - 1), east (c + 1) and west (c - 1) neighbours, each N(v) = v / sqrt(max((v.x^2 + v.y^2) + v.z^2, 2^-23))
+ * (l2_normalize); n1 = N(E x N), n2 = N(W x S), n3 = N(N x W), n4 = N(S x E), n = N((((n1 + n2) + n3) + n4) / 4).  normals: float32
+ * [H][W][3], rounded from float64; border cells (0, 0, 0); a NaN altitude makes the (up to five) normals that read it NaN.
+ * AXES: as upstream y grows with the ROW, so the frame is left-handed and flat ground gives n = (0, 0, -1); the angle between
+ * two grids does not depend on that.
+ *
+ * bn_normal_angle: replaces calc_nr_diff (sat_utils.py:164-173, normalize=False), the nanmean of :341 and MaskDoD (:278-297, :346).
+ * n1, n2: float32 [H][W][3].  a = acos(clamp((n1.x n2.x + n1.y n2.y) + n1.z n2.z, -1, 1)) 180 / pi in float64; angle: float32 [H][W]
+ * (nullable).  border = 0 is the reference (border normals are zero, so border cells count as 90 degrees); border = 1 writes NaN
+ * there and leaves them out.  mask: uint8 [H][W], nonzero = inside; NULL: every cell is inside.  sums: int64 [6] the CALLER zeroes,
+ * += {sum, count} over all cells, the inside cells and the outside cells, sum of llrint(a 2^20); NaN cells are left out. */
+#define BN_SSIM_MAX_WINDOW 11
+int bn_ssim_map(const float *pred, const float *gt, int32_t C, int32_t H, int32_t W, int64_t plane_stride, int64_t row_stride,
+                int64_t col_stride, const uint8_t *mask, double div, double max_val, int32_t window, const double *g, int32_t row0,
+                int32_t row1, float *map, long long *sums, void *stream);
+int bn_grid_normals(const float *z, int32_t H, int32_t W, double resolution, float *normals, void *stream);
+int bn_normal_angle(const float *n1, const float *n2, int32_t H, int32_t W, const uint8_t *mask, int32_t border, float *angle,
+                    long long *sums, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
