@@ -14,9 +14,11 @@ from .relight import render_surface, relight, relight_image, brdf_lobe, directio
 from .shadows import render_shadow_surface, relight_shadowed, relight_image_shadowed, sun_visibility  # noqa: F401
 from .dsm import SceneFrame, Grid, point_cloud, altitude_image, DsmAccumulator, dsm_image, altitude_mae  # noqa: F401
 from .metrics import image_psnr, image_ssim, dsm_normals, normal_angle_mae, score_view  # noqa: F401
+from .register import register_xy, apply_registration, altitude_mae_xy  # noqa: F401
 from ._lib import set_deterministic  # noqa: F401
 
 __all__ = ["SpSBRDFNeRF", "load_model", "render_rays", "inference", "get_z_vals", "cal_weight", "functions", "set_deterministic",
            "render_surface", "relight", "relight_image", "brdf_lobe", "directions", "render_shadow_surface", "relight_shadowed",
            "relight_image_shadowed", "sun_visibility", "SceneFrame", "Grid", "point_cloud", "altitude_image", "DsmAccumulator",
-           "dsm_image", "altitude_mae", "image_psnr", "image_ssim", "dsm_normals", "normal_angle_mae", "score_view"]
+           "dsm_image", "altitude_mae", "image_psnr", "image_ssim", "dsm_normals", "normal_angle_mae", "score_view",
+           "register_xy", "apply_registration", "altitude_mae_xy"]

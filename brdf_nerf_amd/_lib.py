@@ -63,6 +63,7 @@ BN_SHADE_LAMBERT, BN_SHADE_RPV, BN_SHADE_HAPKE, BN_SHADE_MICROFACET = 0, 1, 2, 3
 BN_DSM_DISC, BN_DSM_SQUARE = 0, 1
 BN_DSM_MAX_RADIUS = 4
 BN_SSIM_MAX_WINDOW = 11
+BN_NCC_MAX_RANGE, BN_NCC_MAX_SCALE, BN_NCC_MAX_SHIFT, BN_NCC_MAX_CELLS = 8, 16, 1 << 20, 1 << 22
 
 
 class NormalReg(C.Structure):         # bn_normal_reg
@@ -162,6 +163,10 @@ _SIGS = {
                               C.c_double, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, fptr, fptr, fptr]),
     "bn_grid_normals": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_double, fptr, fptr]),
     "bn_normal_angle": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, fptr, C.c_int32, fptr, fptr, fptr]),
+    "bn_grid_halve": (C.c_int, [fptr, C.c_int32, C.c_int32, fptr, fptr]),
+    "bn_ncc_moments": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                 C.c_int32, fptr, fptr, fptr]),
+    "bn_dsm_shift_diff": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, fptr, fptr, fptr, fptr, fptr]),
     "bn_lambert_tail": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, fptr, fptr, C.c_int64, fptr,
                                   C.c_int64, fptr, C.c_int64, fptr, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, fptr, fptr,
                                   C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),

@@ -202,8 +202,9 @@ def altitude_mae(dsm, gt, mask=None):
       pred_r = pred + nanmean(gt - pred) ;  diff = pred_r - gt ;  mae = nanmean(|diff|)
     mask (bool, True inside; MaskDoD, sat_utils.py:278-297): also mae_in over the cells inside and mae_out over the others.
     Plain torch on the tensors' device (host tensors too).  -> {"mae", "shift", "diff"} (+ "mae_in", "mae_out").
-    Not covered: the xy registration of dsmr, GeoTIFF I/O and the nearest-neighbour hole filling of save_dsm_grid.  The
-    normal-angle MAE (mae_nr) is metrics.normal_angle_mae."""
+    The xy registration of dsmr - the path the reference takes when dsmr imports - is register.altitude_mae_xy.  Not covered:
+    GeoTIFF I/O and the nearest-neighbour hole filling of save_dsm_grid.  The normal-angle MAE (mae_nr) is
+    metrics.normal_angle_mae."""
     pred, gt = torch.as_tensor(dsm).double(), torch.as_tensor(gt).double()
     if pred.shape != gt.shape:
         raise ValueError(f"altitude_mae: dsm {tuple(pred.shape)} and ground truth {tuple(gt.shape)} are not on one grid")

@@ -783,6 +783,55 @@ def normal_angle(n1, n2, mask=None, border=0, sums=None, want_map=True):
     return angle, sums
 
 
+def grid_halve(src):
+    """One level of the registration pyramid (bn_grid_halve): src (H, W) float64 -> (ceil(H / 2), ceil(W / 2)) float64, the mean of
+    the finite cells of upstream's 2 x 2 box, NaN where there is none."""
+    assert src.is_cuda and src.dtype == torch.float64 and src.dim() == 2
+    src = src.contiguous()
+    H, W = src.shape
+    out = torch.empty(((H + 1) // 2, (W + 1) // 2), dtype=torch.float64, device=src.device)
+    L.check(L.lib().bn_grid_halve(_p(src), H, W, _p(out), _stream()), "bn_grid_halve")
+    return out
+
+
+def ncc_moments(u, v, pivot, k, dx0, dy0, r, sums=None, skipped=None, rows=None):
+    """The integer moments of every shift of a (2r + 1)^2 window around (dx0, dy0) (bn_ncc_moments): u, v (H, W) float64 on the
+    device -> sums ((2r + 1)^2, 6) int64 = (N, Su, Sv, Suu, Svv, Suv) in scan order (dy outer, dx inner) and skipped (1,) int64,
+    both accumulated into when given; rows = (row0, row1) rows of u (default all)."""
+    H, W = u.shape
+    for t in (u, v):
+        assert t.is_cuda and t.dtype == torch.float64 and t.shape == (H, W) and t.is_contiguous()
+    n = (2 * int(r) + 1) ** 2 if 0 <= int(r) <= L.BN_NCC_MAX_RANGE else 1          # a refused r never reaches the kernel
+    if sums is None:
+        sums = torch.zeros((n, 6), dtype=torch.int64, device=u.device)
+    if skipped is None:
+        skipped = torch.zeros((1,), dtype=torch.int64, device=u.device)
+    assert sums.is_cuda and sums.dtype == torch.int64 and sums.numel() == n * 6 and sums.is_contiguous()
+    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+    L.check(L.lib().bn_ncc_moments(_p(u), _p(v), H, W, float(pivot), int(k), int(dx0), int(dy0), int(r), row0, row1, _p(sums),
+                                   _p(skipped), _stream()), "bn_ncc_moments")
+    return sums, skipped
+
+
+def dsm_shift_diff(pred, gt, dx, dy, b, mask=None, sums=None, want_maps=True):
+    """A DSM shifted by (dx, dy) cells and b metres and its difference to the ground truth (bn_dsm_shift_diff): pred, gt (H, W)
+    float32, mask (H, W) uint8 (nonzero: inside) or None -> rdsm, diff (H, W) float32 (or None, None), sums (6,) int64 = (sum of
+    llrint(|diff| 2^20), count) over all, inside and outside cells, NaN cells left out."""
+    H, W = pred.shape
+    for t in (pred, gt):
+        assert t.is_cuda and t.dtype == torch.float32 and t.shape == (H, W) and t.is_contiguous()
+    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == (H, W) and mask.is_contiguous())
+    if sums is None:
+        sums = torch.zeros((6,), dtype=torch.int64, device=pred.device)
+    assert sums.is_cuda and sums.dtype == torch.int64 and sums.numel() == 6 and sums.is_contiguous()
+    rdsm = torch.empty((H, W), dtype=torch.float32, device=pred.device) if want_maps else None
+    diff = torch.empty((H, W), dtype=torch.float32, device=pred.device) if want_maps else None
+    L.check(L.lib().bn_dsm_shift_diff(_p(pred), _p(gt), H, W, int(dx), int(dy), float(b), _p(mask), _p(rdsm), _p(diff), _p(sums),
+                                      _stream()), "bn_dsm_shift_diff")
+    return rdsm, diff, sums
+
+
 def sample_shade_dirs(desc, X, w, rays_d, sun, view=None, rgb=None, brdf=None, want_brdf=False):
     """ray_shade_dirs for one BRDF per sample (bn_sample_shade_dirs), forward only.  X (R,S,C) depth-sorted field-output rows,
     w (R,S) their weights; rays_d (R,3) view with unit inner stride; sun (K,3); view (K,3) or None (-rays_d).  rgb / brdf: (K,R,3)

@@ -15,8 +15,8 @@ The sums are integers (SSIM in units of 2^-30, angles in units of 2^-20 degree),
 order, on how an image's rows are split (rows=), or on how many GPUs shared the view: ranks merge by one SUM all-reduce.
 
 The SSIM rule (include/brdfnerf_hip.h states it operation by operation) follows kornia 0.5.3 as documented; it was not checked
-against the package, which this project does not depend on.  Not covered: GeoTIFF I/O, the xy registration of dsmr, the hole
-filling of save_dsm_grid, LPIPS (commented out upstream).
+against the package, which this project does not depend on.  The xy registration of dsmr is register.py's (score_view's
+register="xy").  Not covered: GeoTIFF I/O, the hole filling of save_dsm_grid, LPIPS (commented out upstream).
 """
 import math
 
@@ -199,7 +199,7 @@ def _allreduce_sum(t, group):
 
 @torch.no_grad()
 def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=None, grid=None, dsm_mask=None, group=None,
-               window=3, layout="reference", radius=1, footprint="disc", resolution=0.5, **render_kw):
+               window=3, layout="reference", radius=1, footprint="disc", resolution=0.5, register="z", **render_kw):
     """The reference's evaluation line of one view (eval.py:467-479) in one call: psnr, psnr_scl, ssim, ssim_scl and - with a
     `frame` - the DSM, and with `gt_dsm` on that grid mae, mae_in, mae_out (altitude_mae) and mae_nr (normal_angle_mae).
     rays (H W, >= 8), rgbs (H W, 3) the ground truth, mask the view's valid pixels ((H, W) or (H W,)), dsm_mask the DSM's
@@ -208,6 +208,9 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
     rank then splats its own share of the depths exactly as dsm.dsm_image does (same accumulator, same merge), so `dsm` is
     bitwise dsm_image's after the same torch.manual_seed.  Under data parallelism the image is the gathered one; each rank
     scores its own band of rows (image_ssim's rows=) and one SUM all-reduce of the integer triples merges them.
+    register: 'z' - the z-only registration the reference falls back to without dsmr (altitude_mae; normals of the unshifted DSM);
+    'xy' - its real path with dsmr (sat_utils.py:239-252): mae, mae_in, mae_out and shift from register.altitude_mae_xy, mae_nr*
+    from the normals of the REGISTERED DSM, and also "dx", "dy", "rdsm".
     -> {"psnr", "psnr_scl", "ssim", "ssim_scl", "ssim_skipped", "ssim_sums", "rgb", "depth"} (+ "dsm", "count", "grid",
     "skipped" with a frame; + "mae", "mae_in", "mae_out", "mae_nr", "mae_nr_in", "mae_nr_out", "shift" with gt_dsm)."""
     from .distributed import shard_bounds, world_info
@@ -215,6 +218,8 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
     from .evaluate import render_image
     if rays.shape[0] != H * W:
         raise ValueError(f"score_view: {rays.shape[0]} rays for a view of {H} x {W}")
+    if register not in ("z", "xy"):
+        raise ValueError(f"score_view: register {register!r} ('z' or 'xy')")
     if gt_dsm is not None and frame is None:
         raise ValueError("score_view: gt_dsm needs the scene's frame (frame=) to build the DSM it is compared with")
     check_window(window, H, W)
@@ -240,8 +245,14 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
         res.update(dsm=dsm, count=count, grid=grid, skipped=acc.skipped)
         if gt_dsm is not None:
             gt_dsm = torch.as_tensor(gt_dsm).to(dsm.device)
-            alt = altitude_mae(dsm, gt_dsm, mask=dsm_mask)
-            nr = normal_angle_mae(dsm, gt_dsm, grid.resolution, mask=dsm_mask)
+            if register == "xy":
+                from .register import altitude_mae_xy
+                alt = altitude_mae_xy(dsm, gt_dsm, mask=dsm_mask, group=group)
+                nr = normal_angle_mae(alt["rdsm"], gt_dsm, grid.resolution, mask=dsm_mask)
+                res.update(dx=alt["dx"], dy=alt["dy"], rdsm=alt["rdsm"])
+            else:
+                alt = altitude_mae(dsm, gt_dsm, mask=dsm_mask)
+                nr = normal_angle_mae(dsm, gt_dsm, grid.resolution, mask=dsm_mask)
             res.update(mae=alt["mae"], shift=alt["shift"], mae_in=alt.get("mae_in", -1), mae_out=alt.get("mae_out", -1),
                        mae_nr=nr["mae_nr"], mae_nr_in=nr["mae_nr_in"], mae_nr_out=nr["mae_nr_out"])
     return res

@@ -562,6 +562,48 @@ int bn_ssim_map(const float *pred, const float *gt, int32_t C, int32_t H, int32_
 int bn_grid_normals(const float *z, int32_t H, int32_t W, double resolution, float *normals, void *stream);
 int bn_normal_angle(const float *n1, const float *n2, int32_t H, int32_t W, const uint8_t *mask, int32_t border, float *angle,
                     long long *sums, void *stream);
+/* The xy registration of a DSM on its ground truth (additive to ABI 7): dsmr.compute_shift(gt, pred, scaling=False) and
+ * dsmr.apply_shift as sat_utils.py:239-246 call them - the path the reference takes whenever dsmr imports - as three launches.
+ * u is the ground truth, v the prediction, both [H][W] on one grid; a shift (dx, dy) pairs u[j][i] with v[j + dy][i + dx].
+ * Every float64 operation is rounded on its own and every sum is an INTEGER atomic add, as above.
+ *
+ * bn_grid_halve: replaces dsmr.downsample2x (dsmr.py:16-46).  src: float64 [H][W]; dst: float64 [ceil(H / 2)][ceil(W / 2)].
+ * Upstream writes out[j / 2][i / 2] for every input cell and the last write wins, so output cell (J, I) is the mean of the FINITE
+ * cells of the 2 x 2 box whose corner is (j, i) = (2J + 1, 2I + 1) - (2J, .) when 2J + 1 == H, (., 2I) when 2I + 1 == W - cells
+ * outside the image ignored: s = 0.0, then s = s + t in the order (j, i), (j + 1, i), (j, i + 1), (j + 1, i + 1), s / count; NaN
+ * when no cell of the box is finite (an infinite cell counts as missing).
+ *
+ * bn_ncc_moments: replaces the two image passes of dsmr.mean_std (dsmr.py:49-88) for every shift that dsmr.compute_ncc
+ * (:102-117) scans around (dx0, dy0): shift s = (dy - dy0 + r) (2r + 1) + (dx - dx0 + r), dy outer and dx inner as upstream.
+ * A finite cell z has the quantum q = rint((z - pivot) 2^k), a float64 subtraction, an exact scaling and a round to nearest
+ * even; with pivot = floor(min) and span 2^k <= 2^20 (the caller's choice) 0 <= q <= 2^20.  A finite cell whose q falls outside
+ * [0, 2^20] is treated as missing, and skipped[0] += the number of such cells of u and of v in rows [row0, row1) (each cell
+ * once; only a wrong pivot / k makes any).  sums: int64 [(2r + 1)^2][6] the CALLER zeroes, += (N, Su, Sv, Suu, Svv, Suv) = the
+ * sums of 1, qu, qv, qu^2, qv^2, qu qv over the cells (j, i) of u with row0 <= j < row1 where qu and qv = q(v[j + dy][i + dx]) both
+ * exist (v in range and finite).  With at most 2^22 cells a sum of q^2 <= 2^40 stays below 2^63.  The correlation
+ * (N Suv - Su Sv) / sqrt((N Suu - Su^2) (N Svv - Sv^2)) and the z offset (Su - Sv) / (N 2^k) are the host's, in exact integers.
+ * Row ranges that partition [0, H) add up, over launches or devices, to the single launch's integers.
+ *
+ * bn_dsm_shift_diff: replaces dsmr.apply_shift_ (:138-149; a = 1, and its loop variable shadows the coefficient c, so the c i + d j
+ * terms are zero) and `diff = pred_rdsm - gt_dsm` (sat_utils.py:246), the nanmean of :340 and MaskDoD (:278-297, :344-345).
+ * pred, gt: float32 [H][W].  rdsm[j][i] = (float)((double)pred[j + dy][i + dx] + b), NaN where that cell is out of range;
+ * diff = (float)((double)rdsm - (double)gt), the float32 subtraction bit for bit; both float32 [H][W], nullable.  mask: uint8
+ * [H][W], nonzero = inside; NULL: every cell is inside.  sums6: int64 [6] the CALLER zeroes, += {sum, count} over all cells, the
+ * inside cells and the outside cells, sum of llrint(|diff| 2^20); cells whose diff is NaN are left out, and so is a |diff| of
+ * 2^21 m or more (an infinity included), which the sum could not hold.
+ *
+ * Refused (BN_EINVAL): NULL pointers (rdsm, diff and mask may be NULL), H or W < 1, more than 2^22 cells, r outside
+ * [0, BN_NCC_MAX_RANGE], k outside [0, BN_NCC_MAX_SCALE], rows outside [0, H], a pivot or b that is not finite, |dx| or |dy|
+ * above 2^20. */
+#define BN_NCC_MAX_RANGE 8
+#define BN_NCC_MAX_SCALE 16
+#define BN_NCC_MAX_SHIFT (1 << 20)
+#define BN_NCC_MAX_CELLS ((int64_t)1 << 22)
+int bn_grid_halve(const double *src, int32_t H, int32_t W, double *dst, void *stream);
+int bn_ncc_moments(const double *u, const double *v, int32_t H, int32_t W, double pivot, int32_t k, int32_t dx0, int32_t dy0, int32_t r,
+                   int32_t row0, int32_t row1, long long *sums, long long *skipped, void *stream);
+int bn_dsm_shift_diff(const float *pred, const float *gt, int32_t H, int32_t W, int32_t dx, int32_t dy, double b, const uint8_t *mask,
+                      float *rdsm, float *diff, long long *sums6, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
