@@ -13,6 +13,7 @@
 // (no FMA contraction, like brdf.hip: the degenerate-geometry branches must round like the reference's separate ATen ops)
 #pragma clang fp contract(off)
 #include "brdf_eval.h"
+#include "shade_row.h"
 
 namespace {
 
@@ -31,10 +32,8 @@ struct ShadeArgs {
   unsigned long long *nonfinite;        // nullable: a ray whose loss term is not finite contributes nothing (loss 0, gradients 0) and is counted
 };
 
-// KIND: BN_SHADE_LAMBERT / RPV / HAPKE / MICROFACET.  Dual slots: composited normal 0-2, composited albedo 3-5, then the
-// BRDF parameters (RPV: k 6-8, theta 9-11, rhoc 12-14; Hapke: b 6-8, c 9-11, theta 12; microfacet: roughness 6).
-template <int KIND> struct Slots { static constexpr int N = KIND == BN_SHADE_RPV ? 15 : KIND == BN_SHADE_HAPKE ? 13 : 7; };
-
+// KIND: BN_SHADE_LAMBERT / RPV / HAPKE / MICROFACET.  Dual slots (shade_row.h): the normal and albedo slots are seeded at the
+// COMPOSITED normal and albedo.
 template <int KIND> __global__ __launch_bounds__(64) void ray_shade_loss_kernel(const ShadeArgs A) {
   constexpr int N = Slots<KIND>::N;
   typedef Dual<N> D;
@@ -50,47 +49,19 @@ template <int KIND> __global__ __launch_bounds__(64) void ray_shade_loss_kernel(
                         A.sun_d ? A.sun_d[ray * A.sd_stride + 2] : 1.f};
   // upward normal: |sun_z| (spsbrdfnerf.py:260-264); else the sun pass's visibility of the ray's last sample (:354), else 1
   const float irr = (q.cos_irradiance && has_n) ? fabsf(sun[2]) : (q.irr ? q.irr[ray * q.irr_stride] : 1.f);
-  // composited albedo sum_s w (albedo (1 + 2 pad) - pad)   (:270, :275)
   D w[3], out[3];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) w[c] = seed<N>(acc[c] * (1.f + 2.f * pad) - pad * ws, 3 + c);
+  for (int c = 0; c < 3; ++c) w[c] = seed<N>(padded_albedo(acc[c], pad, ws), 3 + c);
   if (KIND == BN_SHADE_LAMBERT) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[c] = w[c];
   } else {
-    const V3<float> lf = {sun[0], sun[1], sun[2]};
     const float *rd = A.rays_d + ray * A.rd_stride;
-    const V3<float> vf = {-rd[0], -rd[1], -rd[2]};
-    // l2_normalize (train_utils.py:28-33) of the composited normal, differentiated with the rest
+    const float view[3] = {-rd[0], -rd[1], -rd[2]};
+    // the normalisation of the composited normal is differentiated with the rest
     const float *an = acc + q.ch_normal;
-    V3<D> nn = {seed<N>(an[0], 0), seed<N>(an[1], 1), seed<N>(an[2], 2)};
-    const D nrm = sqrt_(clamp_min_(dot3(nn, nn), 1.1920928955078125e-07f));
-    V3<D> ns = {nn.x / nrm, nn.y / nrm, nn.z / nrm};
-    const V3<D> l = cst3<N>(lf), v = cst3<N>(vf);
-    if (KIND == BN_SHADE_RPV) {
-      D k[3], th[3], rc[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        k[c] = seed<N>(q.ch_p0 >= 0 ? acc[q.ch_p0 + c] : 0.f, 6 + c);
-        th[c] = seed<N>(q.ch_p1 >= 0 ? acc[q.ch_p1 + c] : 0.f, 9 + c);
-        rc[c] = q.rhoc_is_albedo ? w[c] : seed<N>(q.ch_p2 >= 0 ? acc[q.ch_p2 + c] : 0.f, 12 + c);   // funcH == 2 (:288-291)
-      }
-      rpv_eval<D>(l, v, ns, w, q.ch_p0 >= 0 ? k : nullptr, q.ch_p1 >= 0 ? th : nullptr,
-                  (q.ch_p2 >= 0 || q.rhoc_is_albedo) ? rc : nullptr, out, nullptr);
-    } else if (KIND == BN_SHADE_HAPKE) {
-      D b[3], cc[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        b[c] = seed<N>(q.ch_p0 >= 0 ? acc[q.ch_p0 + c] : 0.f, 6 + c);
-        cc[c] = seed<N>(q.ch_p1 >= 0 ? acc[q.ch_p1 + c] : 0.f, 9 + c);
-      }
-      const D th = seed<N>(q.ch_p2 >= 0 ? acc[q.ch_p2] : 0.f, 12);
-      hapke_eval<D>(l, v, ns, w, q.ch_p0 >= 0 ? b : nullptr, q.ch_p1 >= 0 ? cc : nullptr, q.ch_p2 >= 0 ? &th : nullptr,
-                    q.hpk_scl, q.shell, out, nullptr);
-    } else {
-      const D rg = seed<N>(acc[q.ch_p0], 6);
-      microfacet_eval<D>(l, v, ns, w, rg, q.f0, out, nullptr);
-    }
+    const V3<D> ns = unit_normal<D>({seed<N>(an[0], 0), seed<N>(an[1], 1), seed<N>(an[2], 2)});
+    row_brdf<KIND, D>(q, acc, sun, view, ns, w, [](float v_, int slot) { return seed<N>(v_, slot); }, out);
   }
   // rgb = clamp(irradiance * brdf, 0, 1); SNerfLoss = lambda_rgb * mean over (rays, 3) of (rgb - target)^2
   const float invn = 1.f / (3.f * (float)A.R);
@@ -98,7 +69,7 @@ template <int KIND> __global__ __launch_bounds__(64) void ray_shade_loss_kernel(
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float x = irr * out[c].v;          // (irr == 1 without the cosine term: exact)
-    const float y = isnan(x) ? x : fminf(fmaxf(x, 0.f), 1.f);
+    const float y = clamp_(x, 0.f, 1.f);
     const float e = y - A.rgbs[ray * 3 + c];
     loss += q.lambda_rgb * e * e * invn;
     const float dy = (x >= 0.f && x <= 1.f) ? q.lambda_rgb * 2.f * e * invn : 0.f;
@@ -142,27 +113,7 @@ template <int KIND> __global__ __launch_bounds__(64) void ray_shade_loss_kernel(
     da[c] = dw * (1.f + 2.f * pad);
     dws -= dw * pad;
   }
-  if (KIND != BN_SHADE_LAMBERT) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) da[q.ch_normal + c] = jt(out, db, c);
-    if (KIND == BN_SHADE_RPV) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (q.ch_p0 >= 0) da[q.ch_p0 + c] = jt(out, db, 6 + c);
-        if (q.ch_p1 >= 0) da[q.ch_p1 + c] = jt(out, db, 9 + c);
-        if (q.ch_p2 >= 0 && !q.rhoc_is_albedo) da[q.ch_p2 + c] = jt(out, db, 12 + c);
-      }
-    } else if (KIND == BN_SHADE_HAPKE) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (q.ch_p0 >= 0) da[q.ch_p0 + c] = jt(out, db, 6 + c);
-        if (q.ch_p1 >= 0) da[q.ch_p1 + c] = jt(out, db, 9 + c);
-      }
-      if (q.ch_p2 >= 0) da[q.ch_p2] = jt(out, db, 12);
-    } else {
-      da[q.ch_p0] = jt(out, db, 6);
-    }
-  }
+  if (KIND != BN_SHADE_LAMBERT) scatter_jt<KIND, false>(q, out, db, da);
   A.d_wsum[ray] = dws;
   A.d_depth[ray] = dd;
 }
@@ -177,19 +128,7 @@ extern "C" int bn_ray_shade_loss(const bn_shade_desc *desc, const float *acc, co
                                  float *d_depth, unsigned long long *nonfinite, const float *extra_loss, void *stream) {
   BN_REQUIRE(desc && acc && wsum && depth && rgbs && d_acc && d_wsum && d_depth && R > 0, "ray_shade_loss: null argument");
   const bn_shade_desc &q = *desc;
-  BN_REQUIRE(q.C >= 4 && q.C <= BN_MAX_CH, "ray_shade_loss: C=%d unsupported", q.C);
-  BN_REQUIRE(q.kind >= BN_SHADE_LAMBERT && q.kind <= BN_SHADE_MICROFACET, "ray_shade_loss: kind=%d", q.kind);
-  auto in_range = [&](int ch, int n) { return ch < 0 || (ch >= 4 && ch + n <= q.C); };
-  BN_REQUIRE(in_range(q.ch_normal, 3), "ray_shade_loss: normal channel %d outside [4, %d)", q.ch_normal, q.C);
-  if (q.kind != BN_SHADE_LAMBERT) {
-    BN_REQUIRE(q.ch_normal >= 4 && rays_d, "ray_shade_loss: BRDF shading needs a normal field and the ray directions");
-    const int n2 = q.kind == BN_SHADE_HAPKE ? 1 : 3;
-    const int n0 = q.kind == BN_SHADE_MICROFACET ? 1 : 3;
-    BN_REQUIRE(in_range(q.ch_p0, n0) && in_range(q.ch_p1, 3) && in_range(q.ch_p2, n2), "ray_shade_loss: parameter channels (%d, %d, %d) outside [4, %d)",
-               q.ch_p0, q.ch_p1, q.ch_p2, q.C);
-    BN_REQUIRE(q.kind != BN_SHADE_MICROFACET || q.ch_p0 >= 4, "ray_shade_loss: microfacet needs the roughness channel");
-    BN_REQUIRE(q.kind != BN_SHADE_HAPKE || q.ch_p0 >= 4 || (q.shell >= 1 && q.shell <= 3), "ray_shade_loss: Hapke without b needs shell_hapke in {1,2,3}");
-  }
+  if (int e = shade_desc_check(q, rays_d != nullptr, "ray_shade_loss")) return e;
   BN_REQUIRE(!target_depth || (valid_depth && target_weight && target_std && var), "ray_shade_loss: incomplete depth prior");
   BN_REQUIRE(!(q.lambda_hs > 0.f) || var, "ray_shade_loss: lambda_hs needs the per-ray variance");
   ShadeArgs a;
@@ -201,12 +140,7 @@ extern "C" int bn_ray_shade_loss(const bn_shade_desc *desc, const float *acc, co
   const dim3 grid((unsigned)ceil_div64(R, 64));
   hipStream_t st = (hipStream_t)stream;
   BnProfScope prof_(BN_K_BRDF, st);
-  switch (q.kind) {
-    case BN_SHADE_LAMBERT: ray_shade_loss_kernel<BN_SHADE_LAMBERT><<<grid, 64, 0, st>>>(a); break;
-    case BN_SHADE_RPV: ray_shade_loss_kernel<BN_SHADE_RPV><<<grid, 64, 0, st>>>(a); break;
-    case BN_SHADE_HAPKE: ray_shade_loss_kernel<BN_SHADE_HAPKE><<<grid, 64, 0, st>>>(a); break;
-    default: ray_shade_loss_kernel<BN_SHADE_MICROFACET><<<grid, 64, 0, st>>>(a); break;
-  }
+  shade_dispatch(q, [&](auto kind, auto) { ray_shade_loss_kernel<decltype(kind)::value><<<grid, 64, 0, st>>>(a); });
   BN_LAUNCH_CHECK("ray_shade_loss");
   return 0;
 }

@@ -20,6 +20,7 @@
 // (no FMA contraction, like brdf.hip and ray_tail.hip: one direction must round like bn_ray_shade_loss)
 #pragma clang fp contract(off)
 #include "brdf_eval.h"
+#include "shade_row.h"
 
 namespace {
 
@@ -31,9 +32,7 @@ struct RelightArgs {
   int32_t K, ktile;
 };
 
-// KIND: BN_SHADE_*.  MASK: which of the BRDF's parameter heads exist (bit 0 p0, bit 1 p1, bit 2 p2 - or, for RPV, rhoc = albedo_s):
-// a compile-time constant, so that the nullable-pointer arguments of the BRDF bodies fold away and the parameters stay in
-// registers (a run-time select between a local array and nullptr forces the array into scratch).
+// KIND / MASK: shade_row.h.
 // sun / view [K][3] (view nullptr: -rays_d of the ray, sun mode; else the lobe's view directions) and rgb / brdf [K][R][3] (brdf
 // nullable) are kernel parameters of their own, __restrict__: only then can the compiler know that the stores of the direction loop
 // do not touch the directions, and read sun[k] / view[k] through the scalar cache.
@@ -47,31 +46,20 @@ void ray_shade_dirs_kernel(const RelightArgs A, const float *__restrict__ sun, c
   const float ws = A.wsum[ray];
   const float pad = q.rgb_padding;
   const bool has_n = q.ch_normal >= 0;
-  // ---- the ray's row, once: composited albedo sum_s w (albedo (1 + 2 pad) - pad)   (:270, :275)
+  // ---- the ray's row, once
   float w[3];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) w[c] = acc[c] * (1.f + 2.f * pad) - pad * ws;
+  for (int c = 0; c < 3; ++c) w[c] = padded_albedo(acc[c], pad, ws);
   V3<float> ns = {0.f, 0.f, 1.f}, vray = {0.f, 0.f, 1.f};
   float p0[3] = {0.f, 0.f, 0.f}, p1[3] = {0.f, 0.f, 0.f}, p2[3] = {0.f, 0.f, 0.f};
   if (KIND != BN_SHADE_LAMBERT) {
-    const float *an = acc + q.ch_normal;       // l2_normalize (train_utils.py:28-33) of the composited normal
-    const float nrm = sqrtf(clamp_min_(an[0] * an[0] + an[1] * an[1] + an[2] * an[2], 1.1920928955078125e-07f));
-    ns = {an[0] / nrm, an[1] / nrm, an[2] / nrm};
+    const float *an = acc + q.ch_normal;
+    ns = unit_normal<float>({an[0], an[1], an[2]});
     if (!view) {
       const float *rd = A.rays_d + ray * A.rd_stride;
       vray = {-rd[0], -rd[1], -rd[2]};
     }
-    if (KIND == BN_SHADE_MICROFACET) {
-      p0[0] = acc[q.ch_p0];
-    } else {
-      const int n2 = KIND == BN_SHADE_HAPKE ? 1 : 3;          // Hapke's theta is one channel wide
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (MASK & 1) p0[c] = acc[q.ch_p0 + c];
-        if (MASK & 2) p1[c] = acc[q.ch_p1 + c];
-        if ((MASK & 4) && c < n2) p2[c] = (KIND == BN_SHADE_RPV && q.rhoc_is_albedo) ? w[c] : acc[q.ch_p2 + c];   // funcH == 2 (:288-291)
-      }
-    }
+    row_params<KIND, MASK>(q, acc, w, p0, p1, p2);
   }
   // ---- the tile of directions: k is the same in every lane, sun[k] / view[k] come through the scalar cache
   const int k0 = (int)blockIdx.y * A.ktile;
@@ -88,42 +76,15 @@ void ray_shade_dirs_kernel(const RelightArgs A, const float *__restrict__ sun, c
     // upward normal: |sun_z| (spsbrdfnerf.py:260-264), else 1
     const float irr = (q.cos_irradiance && has_n) ? fabsf(l.z) : 1.f;
     float out[3];
-    if (KIND == BN_SHADE_LAMBERT) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) out[c] = w[c];
-    } else if (KIND == BN_SHADE_RPV) {
-      rpv_eval<float>(l, v, ns, w, (MASK & 1) ? p0 : nullptr, (MASK & 2) ? p1 : nullptr, (MASK & 4) ? p2 : nullptr, out, nullptr);
-    } else if (KIND == BN_SHADE_HAPKE) {
-      hapke_eval<float>(l, v, ns, w, (MASK & 1) ? p0 : nullptr, (MASK & 2) ? p1 : nullptr, (MASK & 4) ? p2 : nullptr, q.hpk_scl,
-                        q.shell, out, nullptr);
-    } else {
-      microfacet_eval<float>(l, v, ns, w, p0[0], q.f0, out, nullptr);
-    }
+    brdf_value<KIND, MASK>(q, l, v, ns, w, p0, p1, p2, out);
     float *rgb = rgb_out + (int64_t)k * plane + ray * 3;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float x = irr * out[c];            // (irr == 1 without the cosine term: exact)
-      rgb[c] = isnan(x) ? x : fminf(fmaxf(x, 0.f), 1.f);
-    }
+    for (int c = 0; c < 3; ++c) rgb[c] = clamp_(irr * out[c], 0.f, 1.f);            // (irr == 1 without the cosine term: exact)
     if (brdf_out) {
       float *b = brdf_out + (int64_t)k * plane + ray * 3;
 #pragma unroll
       for (int c = 0; c < 3; ++c) b[c] = out[c];
     }
-  }
-}
-
-template <int KIND> void launch_masked(int mask, dim3 grid, hipStream_t st, const RelightArgs &a, const float *sun, const float *view,
-                                       float *rgb, float *brdf) {
-  switch (mask) {
-    case 0: ray_shade_dirs_kernel<KIND, 0><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 1: ray_shade_dirs_kernel<KIND, 1><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 2: ray_shade_dirs_kernel<KIND, 2><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 3: ray_shade_dirs_kernel<KIND, 3><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 4: ray_shade_dirs_kernel<KIND, 4><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 5: ray_shade_dirs_kernel<KIND, 5><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 6: ray_shade_dirs_kernel<KIND, 6><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    default: ray_shade_dirs_kernel<KIND, 7><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
   }
 }
 
@@ -140,7 +101,7 @@ struct SampleDirsArgs {
 constexpr int SAMPLE_KT = 8;
 
 // A lane owns a ray.  Outer loop: the ray's samples in ascending s, each row loaded and unpacked ONCE - the raw normal, the raw
-// albedo and the parameter channels, what sample_brdf.hip's row_brdf hands to the same *_eval bodies.  Inner loop: the tile's
+// albedo and the parameter channels, what sample_brdf.hip hands to the same *_eval bodies.  Inner loop: the tile's
 // directions (wave-uniform, through the scalar cache as above).  Every (ray, direction, channel) has one fp32 accumulator that
 // takes its terms in ascending s - no atomics, no cross-lane step - so a result's bits depend on nothing but its own ray and
 // direction: not on the tile, the ray block, K or the caller's chunking.  No sample is skipped: 0 * inf stays the NaN of the
@@ -176,17 +137,7 @@ void sample_shade_dirs_kernel(const SampleDirsArgs A, const float *__restrict__ 
     const V3<float> ns = {x[q.ch_normal], x[q.ch_normal + 1], x[q.ch_normal + 2]};
     float w[3] = {x[0], x[1], x[2]};
     float p0[3] = {0.f, 0.f, 0.f}, p1[3] = {0.f, 0.f, 0.f}, p2[3] = {0.f, 0.f, 0.f};
-    if (KIND == BN_SHADE_MICROFACET) {
-      p0[0] = x[q.ch_p0];
-    } else {
-      const int n2 = KIND == BN_SHADE_HAPKE ? 1 : 3;          // Hapke's theta is one channel wide
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (MASK & 1) p0[c] = x[q.ch_p0 + c];
-        if (MASK & 2) p1[c] = x[q.ch_p1 + c];
-        if ((MASK & 4) && c < n2) p2[c] = (KIND == BN_SHADE_RPV && q.rhoc_is_albedo) ? w[c] : x[q.ch_p2 + c];   // funcH == 2 (:288-291)
-      }
-    }
+    row_params<KIND, MASK>(q, x, w, p0, p1, p2);
 #pragma nounroll
     for (int j = 0; j < SAMPLE_KT; ++j) {
       float r0 = ar[0][0], r1 = ar[0][1], r2 = ar[0][2], b0 = ab[0][0], b1 = ab[0][1], b2 = ab[0][2];
@@ -200,14 +151,7 @@ void sample_shade_dirs_kernel(const SampleDirsArgs A, const float *__restrict__ 
         }
         const float irr = cosi ? fabsf(l.z) : 1.f;           // upward normal: |sun_z| (spsbrdfnerf.py:260-264), else 1
         float out[3];
-        if (KIND == BN_SHADE_RPV) {
-          rpv_eval<float>(l, v, ns, w, (MASK & 1) ? p0 : nullptr, (MASK & 2) ? p1 : nullptr, (MASK & 4) ? p2 : nullptr, out, nullptr);
-        } else if (KIND == BN_SHADE_HAPKE) {
-          hapke_eval<float>(l, v, ns, w, (MASK & 1) ? p0 : nullptr, (MASK & 2) ? p1 : nullptr, (MASK & 4) ? p2 : nullptr, q.hpk_scl,
-                            q.shell, out, nullptr);
-        } else {
-          microfacet_eval<float>(l, v, ns, w, p0[0], q.f0, out, nullptr);
-        }
+        brdf_value<KIND, MASK>(q, l, v, ns, w, p0, p1, p2, out);
         // (w bp) irr, the reference's order (:350-352); irr == 1 without the cosine term: exact
         r0 = r0 + ws * (out[0] * gain - pad) * irr;
         r1 = r1 + ws * (out[1] * gain - pad) * irr;
@@ -232,30 +176,13 @@ void sample_shade_dirs_kernel(const SampleDirsArgs A, const float *__restrict__ 
     if (j < n) {
       float *rgb = rgb_out + (int64_t)(k0 + j) * A.rgb_plane + ray * 3;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float v_ = ar[j][c];
-        rgb[c] = isnan(v_) ? v_ : fminf(fmaxf(v_, 0.f), 1.f);
-      }
+      for (int c = 0; c < 3; ++c) rgb[c] = clamp_(ar[j][c], 0.f, 1.f);
       if (brdf_out) {
         float *b = brdf_out + (int64_t)(k0 + j) * A.brdf_plane + ray * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) b[c] = ab[j][c];
       }
     }
-  }
-}
-
-template <int KIND> void launch_sample_masked(int mask, dim3 grid, hipStream_t st, const SampleDirsArgs &a, const float *sun,
-                                              const float *view, float *rgb, float *brdf) {
-  switch (mask) {
-    case 0: sample_shade_dirs_kernel<KIND, 0><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 1: sample_shade_dirs_kernel<KIND, 1><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 2: sample_shade_dirs_kernel<KIND, 2><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 3: sample_shade_dirs_kernel<KIND, 3><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 4: sample_shade_dirs_kernel<KIND, 4><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 5: sample_shade_dirs_kernel<KIND, 5><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case 6: sample_shade_dirs_kernel<KIND, 6><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    default: sample_shade_dirs_kernel<KIND, 7><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
   }
 }
 
@@ -266,42 +193,22 @@ extern "C" int bn_ray_shade_dirs(const bn_shade_desc *desc, const float *acc, co
                                  float *brdf, void *stream) {
   BN_REQUIRE(desc && acc && wsum && sun && rgb && R > 0 && K > 0, "ray_shade_dirs: null argument");
   const bn_shade_desc &q = *desc;
-  BN_REQUIRE(q.C >= 4 && q.C <= BN_MAX_CH, "ray_shade_dirs: C=%d unsupported", q.C);
-  BN_REQUIRE(q.kind >= BN_SHADE_LAMBERT && q.kind <= BN_SHADE_MICROFACET, "ray_shade_dirs: kind=%d", q.kind);
+  if (int e = shade_desc_check(q, rays_d || view, "ray_shade_dirs")) return e;
   BN_REQUIRE(!q.irr, "ray_shade_dirs: a per-ray irradiance of the sun pass depends on the sun direction (not relightable)");
-  auto in_range = [&](int ch, int n) { return ch < 0 || (ch >= 4 && ch + n <= q.C); };
-  BN_REQUIRE(in_range(q.ch_normal, 3), "ray_shade_dirs: normal channel %d outside [4, %d)", q.ch_normal, q.C);
-  if (q.kind != BN_SHADE_LAMBERT) {
-    BN_REQUIRE(q.ch_normal >= 4 && (rays_d || view), "ray_shade_dirs: BRDF shading needs a normal field and the ray or view directions");
-    const int n2 = q.kind == BN_SHADE_HAPKE ? 1 : 3;
-    const int n0 = q.kind == BN_SHADE_MICROFACET ? 1 : 3;
-    BN_REQUIRE(in_range(q.ch_p0, n0) && in_range(q.ch_p1, 3) && in_range(q.ch_p2, n2), "ray_shade_dirs: parameter channels (%d, %d, %d) outside [4, %d)",
-               q.ch_p0, q.ch_p1, q.ch_p2, q.C);
-    BN_REQUIRE(q.kind != BN_SHADE_MICROFACET || q.ch_p0 >= 4, "ray_shade_dirs: microfacet needs the roughness channel");
-    BN_REQUIRE(q.kind != BN_SHADE_HAPKE || q.ch_p0 >= 4 || (q.shell >= 1 && q.shell <= 3), "ray_shade_dirs: Hapke without b needs shell_hapke in {1,2,3}");
-  }
   BN_REQUIRE(R <= (int64_t)64 * 0x7fffffff, "ray_shade_dirs: R=%lld too large", (long long)R);
   RelightArgs a;
   a.d = q; a.acc = acc; a.wsum = wsum; a.rays_d = rays_d; a.rd_stride = rd_stride; a.R = R; a.K = K;
-  // Direction tile: as long as possible (the ray's row is loaded and prepared once per tile) while ray blocks x tiles still give
-  // every CU several waves - an image has thousands of ray blocks and takes all its directions in one tile (up to 32), a lobe has
-  // one ray block and tens of thousands of directions.  Every (direction, ray) is computed on its own: the tiling changes no bit.
+  // an image has thousands of ray blocks and takes all its directions in one tile (up to 32), a lobe has one ray block and tens of
+  // thousands of directions
   const int64_t blocks = ceil_div64(R, 64);
-  int64_t kt = (int64_t)K * blocks / 2048;
-  kt = kt < 1 ? 1 : (kt > 32 ? 32 : kt);
-  const int64_t need = ceil_div64(K, 65535);               // gridDim.y <= 65535
-  if (kt < need) kt = need;
+  const int64_t kt = dir_tile(K, blocks, 32, 1);
   a.ktile = (int32_t)kt;
   const dim3 grid((unsigned)blocks, (unsigned)ceil_div64(K, kt));
   hipStream_t st = (hipStream_t)stream;
   BnProfScope prof_(BN_K_BRDF, st);
-  const int mask = (q.ch_p0 >= 0 ? 1 : 0) | (q.ch_p1 >= 0 ? 2 : 0) | ((q.ch_p2 >= 0 || (q.kind == BN_SHADE_RPV && q.rhoc_is_albedo)) ? 4 : 0);
-  switch (q.kind) {
-    case BN_SHADE_LAMBERT: ray_shade_dirs_kernel<BN_SHADE_LAMBERT, 0><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-    case BN_SHADE_RPV: launch_masked<BN_SHADE_RPV>(mask, grid, st, a, sun, view, rgb, brdf); break;
-    case BN_SHADE_HAPKE: launch_masked<BN_SHADE_HAPKE>(mask, grid, st, a, sun, view, rgb, brdf); break;
-    default: ray_shade_dirs_kernel<BN_SHADE_MICROFACET, 1><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf); break;
-  }
+  shade_dispatch(q, [&](auto kind, auto mask) {
+    ray_shade_dirs_kernel<decltype(kind)::value, decltype(mask)::value><<<grid, 64, 0, st>>>(a, sun, view, rgb, brdf);
+  });
   BN_LAUNCH_CHECK("ray_shade_dirs");
   return 0;
 }
@@ -311,45 +218,34 @@ extern "C" int bn_sample_shade_dirs(const bn_shade_desc *desc, const float *X, c
                                     float *brdf, int64_t brdf_plane, void *stream) {
   BN_REQUIRE(desc && X && w && sun && rgb && R > 0 && S > 0 && K > 0, "sample_shade_dirs: null argument");
   const bn_shade_desc &q = *desc;
-  BN_REQUIRE(q.C >= 4 && q.C <= BN_MAX_CH, "sample_shade_dirs: C=%d unsupported", q.C);
   BN_REQUIRE(q.kind > BN_SHADE_LAMBERT && q.kind <= BN_SHADE_MICROFACET,
              "sample_shade_dirs: kind=%d (a Lambertian colour is a function of the composited sums: bn_ray_shade_dirs)", q.kind);
+  if (int e = shade_desc_check(q, rays_d || view, "sample_shade_dirs")) return e;
   BN_REQUIRE(!q.irr, "sample_shade_dirs: an irradiance of the sun pass depends on the sun direction (not relightable)");
-  auto in_range = [&](int ch, int n) { return ch < 0 || (ch >= 4 && ch + n <= q.C); };
-  BN_REQUIRE(in_range(q.ch_normal, 3), "sample_shade_dirs: normal channel %d outside [4, %d)", q.ch_normal, q.C);
-  BN_REQUIRE(q.ch_normal >= 4 && (rays_d || view), "sample_shade_dirs: BRDF shading needs a normal field and the ray or view directions");
-  const int n2 = q.kind == BN_SHADE_HAPKE ? 1 : 3;
-  const int n0 = q.kind == BN_SHADE_MICROFACET ? 1 : 3;
-  BN_REQUIRE(in_range(q.ch_p0, n0) && in_range(q.ch_p1, 3) && in_range(q.ch_p2, n2), "sample_shade_dirs: parameter channels (%d, %d, %d) outside [4, %d)",
-             q.ch_p0, q.ch_p1, q.ch_p2, q.C);
-  BN_REQUIRE(q.kind != BN_SHADE_MICROFACET || q.ch_p0 >= 4, "sample_shade_dirs: microfacet needs the roughness channel");
-  BN_REQUIRE(q.kind != BN_SHADE_HAPKE || q.ch_p0 >= 4 || (q.shell >= 1 && q.shell <= 3), "sample_shade_dirs: Hapke without b needs shell_hapke in {1,2,3}");
   BN_REQUIRE(R <= (int64_t)64 * 0x7fffffff, "sample_shade_dirs: R=%lld too large", (long long)R);
   BN_REQUIRE(rgb_plane >= R * 3 && (!brdf || brdf_plane >= R * 3), "sample_shade_dirs: planes (%lld, %lld) shorter than R * 3 = %lld",
              (long long)rgb_plane, (long long)brdf_plane, (long long)(R * 3));
   SampleDirsArgs a;
   a.d = q; a.X = X; a.w = w; a.rays_d = rays_d; a.rd_stride = rd_stride; a.R = R; a.rgb_plane = rgb_plane; a.brdf_plane = brdf_plane;
   a.S = S;
-  // Direction tile: as long as the accumulators allow while ray blocks x tiles still fill the CUs (the rows of a ray are read
-  // once per tile).  Every (direction, ray) is summed on its own: the tiling changes no bit.
+  // The tile is capped by the accumulators, so gridDim.y <= 65535 cannot be met by a longer tile: more directions than a grid of
+  // full tiles holds take more launches (and the tile is that of such a grid)
   const int64_t blocks = ceil_div64(R, 64);
-  int64_t kt = (int64_t)K * blocks / 2048;
-  kt = kt < 1 ? 1 : (kt > SAMPLE_KT ? SAMPLE_KT : kt);
+  const int64_t grid_k = (int64_t)65535 * SAMPLE_KT;
+  const int64_t kt = dir_tile(K < grid_k ? K : grid_k, blocks, SAMPLE_KT, 1);
   a.ktile = (int32_t)kt;
   hipStream_t st = (hipStream_t)stream;
   BnProfScope prof_(BN_K_BRDF, st);
-  const int mask = (q.ch_p0 >= 0 ? 1 : 0) | (q.ch_p1 >= 0 ? 2 : 0) | ((q.ch_p2 >= 0 || (q.kind == BN_SHADE_RPV && q.rhoc_is_albedo)) ? 4 : 0);
-  const int64_t per_launch = 65535 * kt;                   // gridDim.y <= 65535: more directions take more launches
+  const int64_t per_launch = 65535 * kt;
   for (int64_t kb = 0; kb < K; kb += per_launch) {
     a.K = (int32_t)(K - kb < per_launch ? K - kb : per_launch);
     const dim3 grid((unsigned)blocks, (unsigned)ceil_div64(a.K, kt));
     const float *sun_b = sun + kb * 3, *view_b = view ? view + kb * 3 : nullptr;
     float *rgb_b = rgb + kb * rgb_plane, *brdf_b = brdf ? brdf + kb * brdf_plane : nullptr;
-    switch (q.kind) {
-      case BN_SHADE_RPV: launch_sample_masked<BN_SHADE_RPV>(mask, grid, st, a, sun_b, view_b, rgb_b, brdf_b); break;
-      case BN_SHADE_HAPKE: launch_sample_masked<BN_SHADE_HAPKE>(mask, grid, st, a, sun_b, view_b, rgb_b, brdf_b); break;
-      default: sample_shade_dirs_kernel<BN_SHADE_MICROFACET, 1><<<grid, 64, 0, st>>>(a, sun_b, view_b, rgb_b, brdf_b); break;
-    }
+    shade_dispatch(q, [&](auto kind, auto mask) {
+      if constexpr (decltype(kind)::value != BN_SHADE_LAMBERT)         // (refused above)
+        sample_shade_dirs_kernel<decltype(kind)::value, decltype(mask)::value><<<grid, 64, 0, st>>>(a, sun_b, view_b, rgb_b, brdf_b);
+    });
   }
   BN_LAUNCH_CHECK("sample_shade_dirs");
   return 0;

@@ -14,6 +14,7 @@
 // (no FMA contraction, like brdf.hip: the degenerate-geometry branches must round like the reference's separate ATen ops)
 #pragma clang fp contract(off)
 #include "brdf_eval.h"
+#include "shade_row.h"
 
 namespace {
 
@@ -31,42 +32,15 @@ struct SampleArgs {
   float *dX;             // backward: [N][C]
 };
 
-template <int KIND> struct SSlots { static constexpr int N = KIND == BN_SHADE_RPV ? 15 : KIND == BN_SHADE_HAPKE ? 13 : 7; };
-
-// the row's BRDF over the scalar type S (float: values; Dual<N>: values + Jacobian).  Slots as in brdf.hip / ray_tail.hip:
-// normal 0-2, albedo 3-5, then RPV k 6-8, theta 9-11, rhoc 12-14 | Hapke b 6-8, c 9-11, theta 12 | microfacet roughness 6.
+// the row's BRDF (shade_row.h row_brdf) at the row's own normal and albedo, as they are stored
 template <int KIND, typename S, typename Seed>
-__device__ __forceinline__ void row_brdf(const bn_shade_desc &q, const float *x, const float (&sun)[3], const float (&view)[3], Seed seed_,
-                                         S (&out)[3]) {
+__device__ __forceinline__ void raw_row_brdf(const bn_shade_desc &q, const float *x, const float (&sun)[3], const float (&view)[3], Seed seed_,
+                                             S (&out)[3]) {
   const V3<S> n = {seed_(x[q.ch_normal], 0), seed_(x[q.ch_normal + 1], 1), seed_(x[q.ch_normal + 2], 2)};
   S w[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) w[c] = seed_(x[c], 3 + c);
-  const V3<S> l = {cst(w[0], sun[0]), cst(w[0], sun[1]), cst(w[0], sun[2])}, v = {cst(w[0], view[0]), cst(w[0], view[1]), cst(w[0], view[2])};
-  if (KIND == BN_SHADE_RPV) {
-    S k[3], th[3], rc[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      k[c] = seed_(q.ch_p0 >= 0 ? x[q.ch_p0 + c] : 0.f, 6 + c);
-      th[c] = seed_(q.ch_p1 >= 0 ? x[q.ch_p1 + c] : 0.f, 9 + c);
-      rc[c] = q.rhoc_is_albedo ? w[c] : seed_(q.ch_p2 >= 0 ? x[q.ch_p2 + c] : 0.f, 12 + c);      // funcH == 2 (spsbrdfnerf.py:288-291)
-    }
-    rpv_eval<S>(l, v, n, w, q.ch_p0 >= 0 ? k : nullptr, q.ch_p1 >= 0 ? th : nullptr, (q.ch_p2 >= 0 || q.rhoc_is_albedo) ? rc : nullptr,
-                out, nullptr);
-  } else if (KIND == BN_SHADE_HAPKE) {
-    S b[3], cc[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      b[c] = seed_(q.ch_p0 >= 0 ? x[q.ch_p0 + c] : 0.f, 6 + c);
-      cc[c] = seed_(q.ch_p1 >= 0 ? x[q.ch_p1 + c] : 0.f, 9 + c);
-    }
-    const S th = seed_(q.ch_p2 >= 0 ? x[q.ch_p2] : 0.f, 12);
-    hapke_eval<S>(l, v, n, w, q.ch_p0 >= 0 ? b : nullptr, q.ch_p1 >= 0 ? cc : nullptr, q.ch_p2 >= 0 ? &th : nullptr, q.hpk_scl, q.shell, out,
-                  nullptr);
-  } else {
-    const S rg = seed_(x[q.ch_p0], 6);
-    microfacet_eval<S>(l, v, n, w, rg, q.f0, out, nullptr);
-  }
+  row_brdf<KIND, S>(q, x, sun, view, n, w, seed_, out);
 }
 
 template <int KIND, bool BWD> __global__ __launch_bounds__(128) void sample_brdf_kernel(const SampleArgs A) {
@@ -105,7 +79,7 @@ template <int KIND, bool BWD> __global__ __launch_bounds__(128) void sample_brdf
   }
   if constexpr (!BWD) {
     float out[3];
-    row_brdf<KIND, float>(q, x, sun, view, [](float v_, int) { return v_; }, out);
+    raw_row_brdf<KIND, float>(q, x, sun, view, [](float v_, int) { return v_; }, out);
     float *b = A.B + row * A.b_stride;
     if (A.b_stride == C)
       for (int c = 4; c < C; ++c) b[c] = x[c];
@@ -113,10 +87,10 @@ template <int KIND, bool BWD> __global__ __launch_bounds__(128) void sample_brdf
     for (int c = 0; c < 3; ++c) b[c] = (out[c] * gain - pad) * irr;
     b[3] = x[3];
   } else {
-    constexpr int NS = SSlots<KIND>::N;
+    constexpr int NS = Slots<KIND>::N;
     typedef Dual<NS> D;
     D out[3];
-    row_brdf<KIND, D>(q, x, sun, view, [](float v_, int slot) { return seed<NS>(v_, slot); }, out);
+    raw_row_brdf<KIND, D>(q, x, sun, view, [](float v_, int slot) { return seed<NS>(v_, slot); }, out);
     const float *db_ = A.dB + row * A.b_stride;
     const float db[3] = {db_[0] * gain * irr, db_[1] * gain * irr, db_[2] * gain * irr};
     float *dx = A.dX + row * C;
@@ -126,27 +100,8 @@ template <int KIND, bool BWD> __global__ __launch_bounds__(128) void sample_brdf
     dx[3] = db_[3];
     for (int c = 4; c < C; ++c) dx[c] = A.b_stride == C ? db_[c] : 0.f;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      dx[c] = jt(out, db, 3 + c);
-      dx[q.ch_normal + c] += jt(out, db, c);
-    }
-    if (KIND == BN_SHADE_RPV) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (q.ch_p0 >= 0) dx[q.ch_p0 + c] += jt(out, db, 6 + c);
-        if (q.ch_p1 >= 0) dx[q.ch_p1 + c] += jt(out, db, 9 + c);
-        if (q.ch_p2 >= 0 && !q.rhoc_is_albedo) dx[q.ch_p2 + c] += jt(out, db, 12 + c);
-      }
-    } else if (KIND == BN_SHADE_HAPKE) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (q.ch_p0 >= 0) dx[q.ch_p0 + c] += jt(out, db, 6 + c);
-        if (q.ch_p1 >= 0) dx[q.ch_p1 + c] += jt(out, db, 9 + c);
-      }
-      if (q.ch_p2 >= 0) dx[q.ch_p2] += jt(out, db, 12);
-    } else {
-      dx[q.ch_p0] += jt(out, db, 6);
-    }
+    for (int c = 0; c < 3; ++c) dx[c] = jt(out, db, 3 + c);
+    scatter_jt<KIND, true>(q, out, db, dx);
   }
 }
 
@@ -154,17 +109,9 @@ int check_args(const bn_shade_desc *desc, const float *X, const float *rays, int
                int64_t n1, int32_t S1, int32_t S2, int32_t stride, const char *what) {
   BN_REQUIRE(desc && X && rays && N > 0, "%s: null argument", what);
   const bn_shade_desc &q = *desc;
-  BN_REQUIRE(q.kind >= BN_SHADE_LAMBERT && q.kind <= BN_SHADE_MICROFACET, "%s: kind=%d", what, q.kind);
-  BN_REQUIRE(q.C >= 4 && q.C <= BN_MAX_CH && (stride == 4 || stride == q.C), "%s: C=%d, row stride %d (4 or C)", what, q.C, stride);
-  auto in_range = [&](int ch, int n) { return ch < 0 || (ch >= 4 && ch + n <= q.C); };
-  const int n2 = q.kind == BN_SHADE_HAPKE ? 1 : 3, n0 = q.kind == BN_SHADE_MICROFACET ? 1 : 3;
-  BN_REQUIRE(in_range(q.ch_normal, 3) && (q.kind == BN_SHADE_LAMBERT || q.ch_normal >= 4), "%s: normal channel %d outside [4, %d)", what,
-             q.ch_normal, q.C);
-  BN_REQUIRE(q.kind == BN_SHADE_LAMBERT || (in_range(q.ch_p0, n0) && in_range(q.ch_p1, 3) && in_range(q.ch_p2, n2)),
-             "%s: parameter channels %d %d %d outside [4, %d)", what, q.ch_p0, q.ch_p1, q.ch_p2, q.C);
+  if (int e = shade_desc_check(q, true, what)) return e;
+  BN_REQUIRE(stride == 4 || stride == q.C, "%s: C=%d, row stride %d (4 or C)", what, q.C, stride);
   BN_REQUIRE(!q.irr || q.irr_stride >= 0, "%s: irradiance stride %lld", what, (long long)q.irr_stride);
-  BN_REQUIRE(q.kind != BN_SHADE_MICROFACET || q.ch_p0 >= 4, "%s: microfacet needs the roughness channel", what);
-  BN_REQUIRE(q.kind != BN_SHADE_HAPKE || q.ch_p0 >= 4 || (q.shell >= 1 && q.shell <= 3), "%s: Hapke without b needs shell_hapke in {1,2,3}", what);
   BN_REQUIRE(ray_stride >= 6 && (sun_col < 0 || sun_col + 3 <= ray_stride), "%s: ray stride %lld, sun column %d", what, (long long)ray_stride, sun_col);
   // every row's ray exists: the blocks are R rays of S1 (and, behind row n1, R rays of S2) samples each
   BN_REQUIRE(R > 0 && S1 > 0 && n1 == R * (int64_t)S1 && (n1 == N || (S2 > 0 && N - n1 == R * (int64_t)S2)),
@@ -175,12 +122,7 @@ int check_args(const bn_shade_desc *desc, const float *X, const float *rays, int
 template <bool BWD> int launch(const SampleArgs &a, hipStream_t st) {
   const dim3 grid((unsigned)ceil_div64(a.N, 128));
   BnProfScope prof_(BN_K_BRDF, st);
-  switch (a.d.kind) {
-    case BN_SHADE_LAMBERT: sample_brdf_kernel<BN_SHADE_LAMBERT, BWD><<<grid, 128, 0, st>>>(a); break;
-    case BN_SHADE_RPV: sample_brdf_kernel<BN_SHADE_RPV, BWD><<<grid, 128, 0, st>>>(a); break;
-    case BN_SHADE_HAPKE: sample_brdf_kernel<BN_SHADE_HAPKE, BWD><<<grid, 128, 0, st>>>(a); break;
-    default: sample_brdf_kernel<BN_SHADE_MICROFACET, BWD><<<grid, 128, 0, st>>>(a); break;
-  }
+  shade_dispatch(a.d, [&](auto kind, auto) { sample_brdf_kernel<decltype(kind)::value, BWD><<<grid, 128, 0, st>>>(a); });
   BN_LAUNCH_CHECK(BWD ? "sample_brdf_backward" : "sample_brdf_forward");
   return 0;
 }

@@ -24,6 +24,7 @@
 // (no FMA contraction: the table must round like the separate ATen operations it replaces, the shading like relight.hip)
 #pragma clang fp contract(off)
 #include "brdf_eval.h"
+#include "shade_row.h"
 
 namespace {
 
@@ -88,7 +89,7 @@ __device__ __forceinline__ float sun_step(const float *zr, const float *sr, int 
   return 1.f - al + 1e-10f;
 }
 
-// KIND / MASK as in relight.hip.  SAMPLES false: one BRDF per ray from the composited sums, rgb = clamp(T_{G-1} BRDF); true: the
+// KIND / MASK: shade_row.h.  SAMPLES false: one BRDF per ray from the composited sums, rgb = clamp(T_{G-1} BRDF); true: the
 // view ray's own rows X [R][G][C] and weights w [R][G], rgb = clamp(sum_s w_s (c_s (1 + 2 pad) - pad) T_s) with c_s the row's
 // albedo (LAMBERT) or its BRDF, one fp32 accumulator per channel fed in ascending s.
 template <int KIND, int MASK, bool SAMPLES> __global__ __launch_bounds__(64)
@@ -119,21 +120,10 @@ void sun_shade_dirs_kernel(const SunShadeArgs A, const float *__restrict__ sun, 
     const float *acc = A.acc + ray * C;
     const float ws = A.wsum[ray];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) wa[c] = acc[c] * (1.f + 2.f * pad) - pad * ws;
-    const float *an = acc + q.ch_normal;       // l2_normalize (train_utils.py:28-33) of the composited normal
-    const float nrm = sqrtf(clamp_min_(an[0] * an[0] + an[1] * an[1] + an[2] * an[2], 1.1920928955078125e-07f));
-    nsa = {an[0] / nrm, an[1] / nrm, an[2] / nrm};
-    if (KIND == BN_SHADE_MICROFACET) {
-      q0[0] = acc[q.ch_p0];
-    } else {
-      const int n2 = KIND == BN_SHADE_HAPKE ? 1 : 3;          // Hapke's theta is one channel wide
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        if (MASK & 1) q0[c] = acc[q.ch_p0 + c];
-        if (MASK & 2) q1[c] = acc[q.ch_p1 + c];
-        if ((MASK & 4) && c < n2) q2[c] = (KIND == BN_SHADE_RPV && q.rhoc_is_albedo) ? wa[c] : acc[q.ch_p2 + c];   // funcH == 2 (:288-291)
-      }
-    }
+    for (int c = 0; c < 3; ++c) wa[c] = padded_albedo(acc[c], pad, ws);
+    const float *an = acc + q.ch_normal;
+    nsa = unit_normal<float>({an[0], an[1], an[2]});
+    row_params<KIND, MASK>(q, acc, wa, q0, q1, q2);
   }
   const float *zr = nullptr, *sr = nullptr;
   const int kbeg = (int)blockIdx.y * A.ktile;
@@ -189,17 +179,7 @@ void sun_shade_dirs_kernel(const SunShadeArgs A, const float *__restrict__ sun, 
           float p0[3] = {0.f, 0.f, 0.f}, p1[3] = {0.f, 0.f, 0.f}, p2[3] = {0.f, 0.f, 0.f};
           if (KIND != BN_SHADE_LAMBERT) {
             ns = {x[q.ch_normal], x[q.ch_normal + 1], x[q.ch_normal + 2]};
-            if (KIND == BN_SHADE_MICROFACET) {
-              p0[0] = x[q.ch_p0];
-            } else {
-              const int n2 = KIND == BN_SHADE_HAPKE ? 1 : 3;
-#pragma unroll
-              for (int c = 0; c < 3; ++c) {
-                if (MASK & 1) p0[c] = x[q.ch_p0 + c];
-                if (MASK & 2) p1[c] = x[q.ch_p1 + c];
-                if ((MASK & 4) && c < n2) p2[c] = (KIND == BN_SHADE_RPV && q.rhoc_is_albedo) ? w[c] : x[q.ch_p2 + c];
-              }
-            }
+            row_params<KIND, MASK>(q, x, w, p0, p1, p2);
           }
 #pragma nounroll
           for (int j = 0; j < KT; ++j) {
@@ -207,20 +187,12 @@ void sun_shade_dirs_kernel(const SunShadeArgs A, const float *__restrict__ sun, 
             if (j < nk) {
               const float u = sun_step(s_z[j] + lane * LD, s_sg[j] + lane * LD, t, last);
               float out[3];
-              if (KIND == BN_SHADE_LAMBERT) {
-                out[0] = w[0]; out[1] = w[1]; out[2] = w[2];
-              } else {
+              V3<float> l = {0.f, 0.f, 1.f};
+              if (KIND != BN_SHADE_LAMBERT) {
                 const float *sk = sun + (int64_t)(kb + j) * 3;
-                const V3<float> l = {sk[0], sk[1], sk[2]};
-                if (KIND == BN_SHADE_RPV) {
-                  rpv_eval<float>(l, vray, ns, w, (MASK & 1) ? p0 : nullptr, (MASK & 2) ? p1 : nullptr, (MASK & 4) ? p2 : nullptr, out, nullptr);
-                } else if (KIND == BN_SHADE_HAPKE) {
-                  hapke_eval<float>(l, vray, ns, w, (MASK & 1) ? p0 : nullptr, (MASK & 2) ? p1 : nullptr, (MASK & 4) ? p2 : nullptr, q.hpk_scl,
-                                    q.shell, out, nullptr);
-                } else {
-                  microfacet_eval<float>(l, vray, ns, w, p0[0], q.f0, out, nullptr);
-                }
+                l = {sk[0], sk[1], sk[2]};
               }
+              brdf_value<KIND, MASK>(q, l, vray, ns, w, p0, p1, p2, out);
               // (w (c (1 + 2 pad) - pad)) T, the reference's order (:270-273, :350-352)
               a0 = a0 + ws * (out[0] * gain - pad) * T;
               a1 = a1 + ws * (out[1] * gain - pad) * T;
@@ -242,14 +214,7 @@ void sun_shade_dirs_kernel(const SunShadeArgs A, const float *__restrict__ sun, 
       const float *sk = sun + (int64_t)kb * 3;
       const V3<float> l = {sk[0], sk[1], sk[2]};
       float out[3];
-      if (KIND == BN_SHADE_RPV) {
-        rpv_eval<float>(l, vray, nsa, wa, (MASK & 1) ? q0 : nullptr, (MASK & 2) ? q1 : nullptr, (MASK & 4) ? q2 : nullptr, out, nullptr);
-      } else if (KIND == BN_SHADE_HAPKE) {
-        hapke_eval<float>(l, vray, nsa, wa, (MASK & 1) ? q0 : nullptr, (MASK & 2) ? q1 : nullptr, (MASK & 4) ? q2 : nullptr, q.hpk_scl,
-                          q.shell, out, nullptr);
-      } else {
-        microfacet_eval<float>(l, vray, nsa, wa, q0[0], q.f0, out, nullptr);
-      }
+      brdf_value<KIND, MASK>(q, l, vray, nsa, wa, q0, q1, q2, out);
 #pragma unroll
       for (int c = 0; c < 3; ++c) st[0][2 + c] = st[0][1] * out[c];
     }
@@ -259,40 +224,11 @@ void sun_shade_dirs_kernel(const SunShadeArgs A, const float *__restrict__ sun, 
         if (j < nk) {
           float *rgb = rgb_out + (int64_t)(kb + j) * A.rgb_plane + ray * 3;
 #pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float v_ = st[j][2 + c];
-            rgb[c] = isnan(v_) ? v_ : fminf(fmaxf(v_, 0.f), 1.f);
-          }
+          for (int c = 0; c < 3; ++c) rgb[c] = clamp_(st[j][2 + c], 0.f, 1.f);
           if (vis_out) vis_out[(int64_t)(kb + j) * A.vis_plane + ray] = st[j][1];
         }
       }
     }
-  }
-}
-
-template <int KIND, bool SAMPLES> void launch_sun_masked(int mask, dim3 grid, hipStream_t st, const SunShadeArgs &a, const float *sun,
-                                                         float *rgb, float *vis) {
-  switch (mask) {
-    case 0: sun_shade_dirs_kernel<KIND, 0, SAMPLES><<<grid, 64, 0, st>>>(a, sun, rgb, vis); break;
-    case 1: sun_shade_dirs_kernel<KIND, 1, SAMPLES><<<grid, 64, 0, st>>>(a, sun, rgb, vis); break;
-    case 2: sun_shade_dirs_kernel<KIND, 2, SAMPLES><<<grid, 64, 0, st>>>(a, sun, rgb, vis); break;
-    case 3: sun_shade_dirs_kernel<KIND, 3, SAMPLES><<<grid, 64, 0, st>>>(a, sun, rgb, vis); break;
-    case 4: sun_shade_dirs_kernel<KIND, 4, SAMPLES><<<grid, 64, 0, st>>>(a, sun, rgb, vis); break;
-    case 5: sun_shade_dirs_kernel<KIND, 5, SAMPLES><<<grid, 64, 0, st>>>(a, sun, rgb, vis); break;
-    case 6: sun_shade_dirs_kernel<KIND, 6, SAMPLES><<<grid, 64, 0, st>>>(a, sun, rgb, vis); break;
-    default: sun_shade_dirs_kernel<KIND, 7, SAMPLES><<<grid, 64, 0, st>>>(a, sun, rgb, vis); break;
-  }
-}
-
-template <bool SAMPLES> void launch_sun(const bn_shade_desc &q, int mask, dim3 grid, hipStream_t st, const SunShadeArgs &a, const float *sun,
-                                        float *rgb, float *vis) {
-  switch (q.kind) {
-    case BN_SHADE_LAMBERT:
-      if (SAMPLES) sun_shade_dirs_kernel<BN_SHADE_LAMBERT, 0, true><<<grid, 64, 0, st>>>(a, sun, rgb, vis);
-      break;
-    case BN_SHADE_RPV: launch_sun_masked<BN_SHADE_RPV, SAMPLES>(mask, grid, st, a, sun, rgb, vis); break;
-    case BN_SHADE_HAPKE: launch_sun_masked<BN_SHADE_HAPKE, SAMPLES>(mask, grid, st, a, sun, rgb, vis); break;
-    default: sun_shade_dirs_kernel<BN_SHADE_MICROFACET, 1, SAMPLES><<<grid, 64, 0, st>>>(a, sun, rgb, vis); break;
   }
 }
 
@@ -318,12 +254,9 @@ extern "C" int bn_sun_shade_dirs(const bn_shade_desc *desc, const float *sigma_s
                                  float *vis, int64_t vis_plane, void *stream) {
   BN_REQUIRE(desc && sigma_sun && z_sun && sun && rgb && R > 0 && K > 0, "sun_shade_dirs: null argument");
   const bn_shade_desc &q = *desc;
-  BN_REQUIRE(q.C >= 4 && q.C <= BN_MAX_CH, "sun_shade_dirs: C=%d unsupported", q.C);
-  BN_REQUIRE(q.kind >= BN_SHADE_LAMBERT && q.kind <= BN_SHADE_MICROFACET, "sun_shade_dirs: kind=%d", q.kind);
+  if (int e = shade_desc_check(q, rays_d != nullptr, "sun_shade_dirs")) return e;
   BN_REQUIRE(!q.irr, "sun_shade_dirs: the descriptor carries a sun-pass irradiance (this call computes it per direction)");
   BN_REQUIRE(G >= 3 && G <= BN_MAX_G, "sun_shade_dirs: G=%d outside [3, %d]", G, BN_MAX_G);
-  auto in_range = [&](int ch, int n) { return ch < 0 || (ch >= 4 && ch + n <= q.C); };
-  BN_REQUIRE(in_range(q.ch_normal, 3), "sun_shade_dirs: normal channel %d outside [4, %d)", q.ch_normal, q.C);
   BN_REQUIRE(!(q.cos_irradiance && q.ch_normal >= 0), "sun_shade_dirs: cos_irradiance with a normal channel - the cosine branch wins and "
              "the sun pass is unused (models/spsbrdfnerf.py:260-266): bn_ray_shade_dirs / bn_sample_shade_dirs");
   BN_REQUIRE((acc != nullptr) != (X != nullptr), "sun_shade_dirs: give either the composited sums (acc, wsum) or the rows (X, w), not %s",
@@ -332,15 +265,6 @@ extern "C" int bn_sun_shade_dirs(const bn_shade_desc *desc, const float *sigma_s
   BN_REQUIRE(samples ? w != nullptr : wsum != nullptr, "sun_shade_dirs: %s", samples ? "rows without their weights w" : "acc without wsum");
   BN_REQUIRE(samples || q.kind != BN_SHADE_LAMBERT, "sun_shade_dirs: a Lambertian colour under per-sample irradiance is a sum over the "
              "samples (models/spsbrdfnerf.py:265-273): give the rows X, w");
-  if (q.kind != BN_SHADE_LAMBERT) {
-    BN_REQUIRE(q.ch_normal >= 4 && rays_d, "sun_shade_dirs: BRDF shading needs a normal field and the ray directions");
-    const int n2 = q.kind == BN_SHADE_HAPKE ? 1 : 3;
-    const int n0 = q.kind == BN_SHADE_MICROFACET ? 1 : 3;
-    BN_REQUIRE(in_range(q.ch_p0, n0) && in_range(q.ch_p1, 3) && in_range(q.ch_p2, n2), "sun_shade_dirs: parameter channels (%d, %d, %d) outside [4, %d)",
-               q.ch_p0, q.ch_p1, q.ch_p2, q.C);
-    BN_REQUIRE(q.kind != BN_SHADE_MICROFACET || q.ch_p0 >= 4, "sun_shade_dirs: microfacet needs the roughness channel");
-    BN_REQUIRE(q.kind != BN_SHADE_HAPKE || q.ch_p0 >= 4 || (q.shell >= 1 && q.shell <= 3), "sun_shade_dirs: Hapke without b needs shell_hapke in {1,2,3}");
-  }
   BN_REQUIRE(R <= (int64_t)64 * 0x7fffffff, "sun_shade_dirs: R=%lld too large", (long long)R);
   BN_REQUIRE(rgb_plane >= R * 3 && (!vis || vis_plane >= R), "sun_shade_dirs: planes (%lld, %lld) shorter than R * 3 = %lld, R = %lld",
              (long long)rgb_plane, (long long)vis_plane, (long long)(R * 3), (long long)R);
@@ -348,23 +272,18 @@ extern "C" int bn_sun_shade_dirs(const bn_shade_desc *desc, const float *sigma_s
   a.d = q; a.sigma = sigma_sun; a.z = z_sun; a.noise = (noise && noise_std != 0.f) ? noise : nullptr; a.noise_std = noise_std;
   a.acc = acc; a.wsum = wsum; a.X = X; a.w = w; a.rays_d = rays_d; a.rd_stride = rd_stride; a.R = R; a.rgb_plane = rgb_plane;
   a.vis_plane = vis_plane; a.G = G; a.K = K;
-  // Directions a block walks one trip after the other (the per-ray mode prepares its row once for all of them): as many as leave
-  // ray blocks x tiles enough to fill the CUs; a multiple of the per-sample mode's trip.  Every (direction, ray) is computed on
-  // its own: the tiling changes no bit.
+  // a block walks its tile one trip after the other (the per-ray mode prepares its row once for all of them)
   const int64_t blocks = ceil_div64(R, 64);
-  const int64_t trip = samples ? SUN_KT : 1;
-  int64_t kt = (int64_t)K * blocks / 2048;
-  kt = kt < 1 ? 1 : (kt > 8 ? 8 : kt);
-  const int64_t need = ceil_div64(K, 65535);               // gridDim.y <= 65535
-  if (kt < need) kt = need;
-  kt = ceil_div64(kt, trip) * trip;
+  const int64_t kt = dir_tile(K, blocks, 8, samples ? SUN_KT : 1);
   a.ktile = (int32_t)kt;
   const dim3 grid((unsigned)blocks, (unsigned)ceil_div64(K, kt));
   hipStream_t st = (hipStream_t)stream;
   BnProfScope prof_(BN_K_BRDF, st);
-  const int mask = (q.ch_p0 >= 0 ? 1 : 0) | (q.ch_p1 >= 0 ? 2 : 0) | ((q.ch_p2 >= 0 || (q.kind == BN_SHADE_RPV && q.rhoc_is_albedo)) ? 4 : 0);
-  if (samples) launch_sun<true>(q, mask, grid, st, a, sun, rgb, vis);
-  else launch_sun<false>(q, mask, grid, st, a, sun, rgb, vis);
+  shade_dispatch(q, [&](auto kind, auto mask) {
+    constexpr int KIND = decltype(kind)::value, MASK = decltype(mask)::value;
+    if (samples) sun_shade_dirs_kernel<KIND, MASK, true><<<grid, 64, 0, st>>>(a, sun, rgb, vis);
+    else if constexpr (KIND != BN_SHADE_LAMBERT) sun_shade_dirs_kernel<KIND, MASK, false><<<grid, 64, 0, st>>>(a, sun, rgb, vis);   // (refused above)
+  });
   BN_LAUNCH_CHECK("sun_shade_dirs");
   return 0;
 }

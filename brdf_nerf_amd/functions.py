@@ -558,6 +558,17 @@ def _strided(t):
     return C.c_void_p(t.data_ptr()), t.stride(0) if t.shape[0] > 1 else 1
 
 
+def _rows3(t, R):
+    """(R,3) float32 view on the device with unit inner stride (copied when the inner stride is not 1) -> (pointer, row stride);
+    None -> (None, 0)."""
+    if t is None:
+        return None, 0
+    assert t.is_cuda and t.dtype == torch.float32 and t.shape == (R, 3)
+    if t.stride(1) != 1:
+        t = t.contiguous()
+    return C.c_void_p(t.data_ptr()), t.stride(0)
+
+
 def _depth_targets(use, valid_depth, target_depth, target_weight, target_std):
     """The DepthLoss inputs as the kernels take them: (pointer, stride) of each of the four 1-d views in turn, all null with the
     term off."""
@@ -661,16 +672,8 @@ def ray_shade_loss(desc, acc, wsum, depth, var, rays_d, sun_d, rgbs, bufs=None, 
     shapes = dict(rgb=(R, 3), d_acc=(R, Cc), d_wsum=(R,), d_depth=(R,))
     o = {k: (b[k] if k in b else torch.empty(sh, dtype=torch.float32, device=acc.device)) for k, sh in shapes.items()}
     dt = _depth_targets(target_depth is not None and desc.lambda_ds > 0, valid_depth, target_depth, target_weight, target_std)
-
-    def rows3(t):
-        if t is None:
-            return None, 0
-        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3
-        if t.stride(1) != 1:
-            t = t.contiguous()
-        return C.c_void_p(t.data_ptr()), t.stride(0)
-    rdp, rds = rows3(rays_d)
-    sdp, sds = rows3(sun_d)
+    rdp, rds = _rows3(rays_d, R)
+    sdp, sds = _rows3(sun_d, R)
     L.check(L.lib().bn_ray_shade_loss(C.byref(desc), _p(acc), _p(wsum), _p(depth), _p(var), rdp, rds, sdp, sds, _p(rgbs), *dt, R,
                                       _p(o["rgb"]), _p(ray_loss), _p(loss_acc),
                                       0 if loss_acc is None else loss_acc.numel(), _p(o["d_acc"]), _p(o["d_wsum"]), _p(o["d_depth"]),
@@ -687,12 +690,7 @@ def ray_shade_dirs(desc, acc, wsum, rays_d, sun, view=None, rgb=None, brdf=None,
     for t in (acc, wsum, sun) + (() if view is None else (view,)):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
     assert wsum.numel() == R and sun.shape == (K, 3) and (view is None or view.shape == (K, 3)) and desc.C == Cc
-    rdp, rds = None, 0
-    if rays_d is not None:
-        assert rays_d.is_cuda and rays_d.dtype == torch.float32 and rays_d.shape == (R, 3)
-        if rays_d.stride(1) != 1:
-            rays_d = rays_d.contiguous()
-        rdp, rds = C.c_void_p(rays_d.data_ptr()), rays_d.stride(0)
+    rdp, rds = _rows3(rays_d, R)
     if rgb is None:
         rgb = torch.empty((K, R, 3), dtype=torch.float32, device=acc.device)
     if brdf is None and want_brdf:
@@ -842,12 +840,7 @@ def sample_shade_dirs(desc, X, w, rays_d, sun, view=None, rgb=None, brdf=None, w
     for t in (X, w, sun) + (() if view is None else (view,)):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
     assert w.shape == (R, S) and sun.shape == (K, 3) and (view is None or view.shape == (K, 3)) and desc.C == Cc
-    rdp, rds = None, 0
-    if rays_d is not None:
-        assert rays_d.is_cuda and rays_d.dtype == torch.float32 and rays_d.shape == (R, 3)
-        if rays_d.stride(1) != 1:
-            rays_d = rays_d.contiguous()
-        rdp, rds = C.c_void_p(rays_d.data_ptr()), rays_d.stride(0)
+    rdp, rds = _rows3(rays_d, R)
     if rgb is None:
         rgb = torch.empty((K, R, 3), dtype=torch.float32, device=X.device)
     if brdf is None and want_brdf:
@@ -905,12 +898,7 @@ def sun_shade_dirs(desc, sigma_sun, z_sun, rays_d, sun, acc=None, wsum=None, X=N
     assert noise is None or noise.shape == (R, G)
     assert acc is None or (acc.shape == (R, desc.C) and wsum is not None and wsum.numel() == R)
     assert X is None or (X.shape == (R, G, desc.C) and w is not None and w.shape == (R, G))
-    rdp, rds = None, 0
-    if rays_d is not None:
-        assert rays_d.is_cuda and rays_d.dtype == torch.float32 and rays_d.shape == (R, 3)
-        if rays_d.stride(1) != 1:
-            rays_d = rays_d.contiguous()
-        rdp, rds = C.c_void_p(rays_d.data_ptr()), rays_d.stride(0)
+    rdp, rds = _rows3(rays_d, R)
     if rgb is None:
         rgb = torch.empty((K, R, 3), dtype=torch.float32, device=dev)
     if vis is None and want_vis:
