@@ -9,7 +9,8 @@ through rasterio / gdal compute the MAE (sat_utils.py:185-350).  Here:
   Grid             the raster: from_cloud (the bounds rule of :665-671) or from_roi (the ground truth's grid, :658-663)
   point_cloud      (east, north, altitude) of every ray in float64 (:613-633); altitude_image its third column (eval.py:170-172)
   DsmAccumulator   bn_dsm_splat into an int64 (sum, count) grid - chunk by chunk, view by view, rank by rank - and bn_dsm_resolve
-  dsm_image        evaluate.render_image's loop with each chunk's depth splatted as it is produced
+  dsm_image        evaluate.render_image's loop with each chunk's depth splatted as it is produced (fill=True: and the holes
+                   filled, fill.fill_holes)
   altitude_mae     the z-registered mean absolute altitude error (sat_utils.py:235, 246, 340-349)
 
 The sums are integer (altitudes in units of 2^-20 m, added atomically), so a DSM's bits do not depend on the order of the rays, on
@@ -164,14 +165,18 @@ class DsmAccumulator:
 
 
 @torch.no_grad()
-def dsm_image(models, args, rays, frame, grid=None, chunk=None, group=None, radius=1, footprint="disc", resolution=0.5, **render_kw):
+def dsm_image(models, args, rays, frame, grid=None, chunk=None, group=None, radius=1, footprint="disc", resolution=0.5, fill=False,
+              **render_kw):
     """evaluate.render_image with the surface model as its output: the same shard bounds, the same chunks and, after the same
     torch.manual_seed, the same draws - `depth` is render_image's depth bit for bit - and each chunk's depth_coarse is splatted
     into the DSM as it is produced; nothing larger than a chunk's outputs is held.  Under data parallelism every rank splats its
     own share and the accumulators are summed (DsmAccumulator.merge): the result is bitwise the single-process one.
     grid=None: the grid comes from the bounds of the cloud (Grid.from_cloud at `resolution`), which needs every depth first - the
     depths are kept (4 bytes per ray) and splatted after the last chunk.  render_kw: apply_brdf, cos_irra_on, ... as render_image.
-    -> {"dsm" (H, W) float32, "count" (H, W) int32, "depth" (R,), "altitude" (R,) float64, "grid", "skipped"}"""
+    fill=True: also the surface model the reference publishes (the *_Grid.tif of save_dsm_grid, eval.py:135-149): every NaN cell
+    replaced by its nearest known cell (fill.fill_holes; with a group each rank fills a band of rows).
+    -> {"dsm" (H, W) float32, "count" (H, W) int32, "depth" (R,), "altitude" (R,) float64, "grid", "skipped"}
+    (+ "dsm_grid" (H, W) float32 without NaN, "holes", "max_dist" with fill)"""
     from .distributed import gather_rows, shard_bounds, world_info
     from .rendering import render_rays
     rank, world = world_info(group)
@@ -192,8 +197,13 @@ def dsm_image(models, args, rays, frame, grid=None, chunk=None, group=None, radi
         acc = DsmAccumulator(grid, rays.device, radius, footprint).add(mine, local, frame)
     acc.merge(group)
     dsm, count = acc.result()
-    return {"dsm": dsm, "count": count, "depth": depth, "altitude": altitude_image(rays, depth, frame), "grid": grid,
-            "skipped": acc.skipped}
+    res = {"dsm": dsm, "count": count, "depth": depth, "altitude": altitude_image(rays, depth, frame), "grid": grid,
+           "skipped": acc.skipped}
+    if fill:
+        from .fill import fill_holes
+        filled = fill_holes(dsm, group=group)
+        res.update(dsm_grid=filled["filled"], holes=filled["holes"], max_dist=filled["max_dist"])
+    return res
 
 
 def altitude_mae(dsm, gt, mask=None):
@@ -203,8 +213,7 @@ def altitude_mae(dsm, gt, mask=None):
     mask (bool, True inside; MaskDoD, sat_utils.py:278-297): also mae_in over the cells inside and mae_out over the others.
     Plain torch on the tensors' device (host tensors too).  -> {"mae", "shift", "diff"} (+ "mae_in", "mae_out").
     The xy registration of dsmr - the path the reference takes when dsmr imports - is register.altitude_mae_xy.  Not covered:
-    GeoTIFF I/O and the nearest-neighbour hole filling of save_dsm_grid.  The normal-angle MAE (mae_nr) is
-    metrics.normal_angle_mae."""
+    GeoTIFF I/O.  The normal-angle MAE (mae_nr) is metrics.normal_angle_mae."""
     pred, gt = torch.as_tensor(dsm).double(), torch.as_tensor(gt).double()
     if pred.shape != gt.shape:
         raise ValueError(f"altitude_mae: dsm {tuple(pred.shape)} and ground truth {tuple(gt.shape)} are not on one grid")

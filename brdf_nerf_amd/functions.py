@@ -830,6 +830,58 @@ def dsm_shift_diff(pred, gt, dx, dy, b, mask=None, sums=None, want_maps=True):
     return rdsm, diff, sums
 
 
+def _fill_grid(name, t, dtype, what, shape=None):
+    """A (H, W) contiguous tensor of `dtype`, 1 to BN_FILL_MAX_SIDE cells a side, or ValueError by name."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: {what} must be a tensor on the device (there is no host path)")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: {what} is {t.dtype}, not {dtype}")
+    if t.dim() != 2 or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} {tuple(t.shape)} is not a contiguous 2-D (H, W) grid")
+    if not (1 <= t.shape[0] <= L.BN_FILL_MAX_SIDE and 1 <= t.shape[1] <= L.BN_FILL_MAX_SIDE):
+        raise ValueError(f"{name}: {what} of {t.shape[0]} x {t.shape[1]} cells (1 to {L.BN_FILL_MAX_SIDE} a side)")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {what} {tuple(t.shape)} is not on the grid {tuple(shape)}")
+    return t
+
+
+def _fill_device(name, *tensors):
+    """The last of the host-side checks, so that a host tensor is refused by what else is wrong with the call first."""
+    if not all(t.is_cuda for t in tensors):
+        raise ValueError(f"{name}: the grids must be on the device (there is no host path)")
+
+
+def grid_nearest_col(src):
+    """The column pass of the hole filling (bn_grid_nearest_col): src (H, W) float32 -> near_row (H, W) int32, per cell the row of
+    the nearest known (not NaN) cell of its column, ties to the smaller row, -1 in a column without one."""
+    _fill_grid("grid_nearest_col", src, torch.float32, "src")
+    _fill_device("grid_nearest_col", src)
+    H, W = src.shape
+    near_row = torch.empty((H, W), dtype=torch.int32, device=src.device)
+    L.check(L.lib().bn_grid_nearest_col(_p(src), H, W, _p(near_row), _stream()), "bn_grid_nearest_col")
+    return near_row
+
+
+def grid_fill(src, near_row, rows=None, want_source=False, want_dist2=False):
+    """The row pass of the hole filling (bn_grid_fill): src (H, W) float32 and its grid_nearest_col -> dst (H, W) float32 (every cell
+    the bits of its nearest known cell), source (H, W) int32 flat index of that cell and dist2 (H, W) int32 (or None), counts (2,)
+    int64 = (holes, largest d2).  rows = (row0, row1): only those rows are written (the others are uninitialised) and counted."""
+    _fill_grid("grid_fill", src, torch.float32, "src")
+    _fill_grid("grid_fill", near_row, torch.int32, "near_row", src.shape)
+    H, W = src.shape
+    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= row0 <= row1 <= H:
+        raise ValueError(f"grid_fill: rows ({row0}, {row1}) outside [0, {H}]")
+    _fill_device("grid_fill", src, near_row)
+    dst = torch.empty((H, W), dtype=torch.float32, device=src.device)
+    source = torch.empty((H, W), dtype=torch.int32, device=src.device) if want_source else None
+    dist2 = torch.empty((H, W), dtype=torch.int32, device=src.device) if want_dist2 else None
+    counts = torch.zeros((2,), dtype=torch.int64, device=src.device)
+    L.check(L.lib().bn_grid_fill(_p(src), _p(near_row), H, W, row0, row1, _p(dst), _p(source), _p(dist2), _p(counts), _stream()),
+            "bn_grid_fill")
+    return dst, source, dist2, counts
+
+
 def sample_shade_dirs(desc, X, w, rays_d, sun, view=None, rgb=None, brdf=None, want_brdf=False):
     """ray_shade_dirs for one BRDF per sample (bn_sample_shade_dirs), forward only.  X (R,S,C) depth-sorted field-output rows,
     w (R,S) their weights; rays_d (R,3) view with unit inner stride; sun (K,3); view (K,3) or None (-rays_d).  rgb / brdf: (K,R,3)

@@ -16,7 +16,7 @@ order, on how an image's rows are split (rows=), or on how many GPUs shared the 
 
 The SSIM rule (include/brdfnerf_hip.h states it operation by operation) follows kornia 0.5.3 as documented; it was not checked
 against the package, which this project does not depend on.  The xy registration of dsmr is register.py's (score_view's
-register="xy").  Not covered: GeoTIFF I/O, the hole filling of save_dsm_grid, LPIPS (commented out upstream).
+register="xy").  Not covered: GeoTIFF I/O, LPIPS (commented out upstream).
 """
 import math
 

@@ -22,8 +22,7 @@ returns its start.  b = (Su - Sv) / (N 2^k) at the final shift of level 0, withi
 The sums are integers, so (dx, dy, b) do not depend on the block order, on how the rows of u are split (rows=) or on how many
 GPUs shared the grid: ranks merge by one SUM all-reduce of the moments per level.
 
-Not covered: GeoTIFF I/O, scaling=True (the reference passes False), sub-cell shifts (upstream has none), the hole filling of
-save_dsm_grid, LPIPS.
+Not covered: GeoTIFF I/O, scaling=True (the reference passes False), sub-cell shifts (upstream has none), LPIPS.
 """
 import math
 

@@ -604,6 +604,41 @@ int bn_ncc_moments(const double *u, const double *v, int32_t H, int32_t W, doubl
                    int32_t row0, int32_t row1, long long *sums, long long *skipped, void *stream);
 int bn_dsm_shift_diff(const float *pred, const float *gt, int32_t H, int32_t W, int32_t dx, int32_t dy, double b, const uint8_t *mask,
                       float *rdsm, float *diff, long long *sums6, void *stream);
+/* The hole filling of a DSM (additive to ABI 7): quickly_interpolate_nans_from_singlechannel_img (eval.py:107-133; scipy's
+ * griddata(method='nearest') over a k-d tree of every known cell) as save_dsm_grid (:135-149) applies it to write the *_Grid.tif,
+ * as two launches in integers: an exact Euclidean distance transform with its feature map.
+ *
+ * THE RULE.  u: float32 [H][W].  A cell is a HOLE if and only if it is NaN (any payload; np.isnan is upstream's test, so +-inf is
+ * a known value and is copied like any other).  The source of a hole (j, i) is the known cell (j', i') that minimises the integer
+ * triple (d2, j', i') lexicographically, d2 = (j - j')^2 + (i - i')^2: the nearest known cell by exact squared Euclidean distance,
+ * and among equidistant ones the one with the lowest row-major index.  A known cell is its own source, d2 = 0.  The output cell
+ * is the source cell's 32 bits, copied without any arithmetic: -0.0, denormals, +-inf and the known cells keep their bits.
+ * The tie rule is this project's: scipy's k-d tree breaks ties by its traversal order, which nobody can state (on a tie upstream
+ * returns the value of SOME known cell at the minimal d2).
+ *
+ * bn_grid_nearest_col: near_row int32 [H][W]; near_row[j][i] = the row j' of the known cell of COLUMN i that minimises
+ * (|j - j'|, j'), or -1 if the column has no known cell.  One lane per column, one sweep down and one sweep up.
+ *
+ * bn_grid_fill: for the cells of rows [row0, row1) the minimum of (dx^2 + dy^2, near_row[j][i'], i') over the columns i' with
+ * near_row[j][i'] >= 0, dx = i - i', dy = j - near_row[j][i'].  That is the rule's minimiser: within one column d2 is minimal
+ * exactly where |dy| is, and the column pass has resolved that column's ties towards the smaller row.  near_row must be
+ * bn_grid_nearest_col's output for the same src.  It writes, in rows [row0, row1) only (other rows are not touched):
+ *   dst     float32 [H][W]             the source cell's bits
+ *   source  int32 [H][W] (nullable)    the flat index j' W + i'
+ *   dist2   int32 [H][W] (nullable)    d2; with H, W <= BN_FILL_MAX_SIDE, d2 < 2^27
+ *   counts  int64 [2] (nullable)       the CALLER zeroes; [0] += the holes of the rows (an integer add), [1] = max([1], largest
+ *                                      d2 of the rows) (an integer max): row ranges that partition [0, H) add and max, over
+ *                                      launches or devices, to the single launch's
+ * On a grid WITHOUT a known cell every cell keeps its bits, source and dist2 are -1 and counts[1] is left alone (the Python
+ * layer refuses such a grid, as upstream's griddata raises on it).
+ * COST: the row pass scans outwards from a cell's own column and stops a side once dx^2 > best d2, so it is bounded by the
+ * distance to the nearest known cell: a dense DSM with holes of a few cells costs a few LDS reads per cell, a grid with a single
+ * known cell W reads per cell.  That is accepted, not defended: the splat leaves holes of a few cells.
+ * Refused (BN_EINVAL): NULL src, near_row or dst, H or W < 1 or > BN_FILL_MAX_SIDE, rows outside [0, H] or row0 > row1. */
+#define BN_FILL_MAX_SIDE 8192
+int bn_grid_nearest_col(const float *src, int32_t H, int32_t W, int32_t *near_row, void *stream);
+int bn_grid_fill(const float *src, const int32_t *near_row, int32_t H, int32_t W, int32_t row0, int32_t row1, float *dst, int32_t *source,
+                 int32_t *dist2, long long *counts, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
