@@ -65,6 +65,7 @@ BN_DSM_MAX_RADIUS = 4
 BN_SSIM_MAX_WINDOW = 11
 BN_NCC_MAX_RANGE, BN_NCC_MAX_SCALE, BN_NCC_MAX_SHIFT, BN_NCC_MAX_CELLS = 8, 16, 1 << 20, 1 << 22
 BN_FILL_MAX_SIDE = 8192
+BN_MAPS_MAX_SAMPLES, BN_MAPS_MAX_CHANNELS = 4096, 64
 
 
 class NormalReg(C.Structure):         # bn_normal_reg
@@ -170,6 +171,9 @@ _SIGS = {
     "bn_dsm_shift_diff": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, fptr, fptr, fptr, fptr, fptr]),
     "bn_grid_nearest_col": (C.c_int, [fptr, C.c_int32, C.c_int32, fptr, fptr]),
     "bn_grid_fill": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fptr, fptr, fptr, fptr, fptr]),
+    "bn_ray_maps": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int64, C.c_int64, C.c_int64, C.c_int32, fptr, C.c_int64, C.c_int64, C.c_int32,
+                              C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),
+    "bn_point_normals": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_int32, fptr, fptr, fptr, fptr]),
     "bn_lambert_tail": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, fptr, fptr, C.c_int64, fptr,
                                   C.c_int64, fptr, C.c_int64, fptr, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, fptr, fptr,
                                   C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),

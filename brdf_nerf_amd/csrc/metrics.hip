@@ -19,6 +19,7 @@
 #include <cmath>
 #include "common.h"
 #include "brdfnerf_hip.h"
+#include "normal_chain.h"
 // every float64 operation below is rounded on its own (see above); the build also passes -ffp-contract=off for this file
 #pragma clang fp contract(off)
 
@@ -29,7 +30,6 @@ constexpr int MAXWIN = BN_SSIM_MAX_WINDOW;
 constexpr int PITCH = TILE + MAXWIN - 1;       // 42
 constexpr double SSIM_FIX = 1073741824.0;      // 2^30
 constexpr double ANGLE_FIX = 1048576.0;        // 2^20
-constexpr double EPS32 = 1.1920928955078125e-07;      // 2^-23: torch.finfo(float32).eps, the floor of l2_normalize
 
 struct SsimArgs {
   const float *pred, *gt;
@@ -116,18 +116,7 @@ void ssim_map_kernel(const SsimArgs A, float *__restrict__ map, unsigned long lo
   }
 }
 
-struct V3 { double x, y, z; };
-
-__device__ __forceinline__ V3 unit(V3 v) {
-  // train_utils.l2_normalize: v / sqrt(max(sum(v^2), eps32)); a NaN norm stays NaN, as torch.maximum keeps it
-  const double n = (v.x * v.x + v.y * v.y) + v.z * v.z;
-  const double d = sqrt(n < EPS32 ? EPS32 : n);
-  return {v.x / d, v.y / d, v.z / d};
-}
-
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
+using normal_chain::V3;       // the per-cell chain lives in normal_chain.h, shared with bn_point_normals (view_maps.hip)
 
 __global__ __launch_bounds__(256)
 void grid_normals_kernel(const float *__restrict__ z, int H, int W, double res, float *__restrict__ out) {
@@ -141,13 +130,10 @@ void grid_normals_kernel(const float *__restrict__ z, int H, int W, double res, 
   }
   // P(r, c) = (c res, r res, z): x grows with the column, y with the ROW (sat_utils.py:178-182)
   const double x0 = (double)c * res, y0 = (double)r * res, z0 = (double)z[cell];
-  const V3 S = unit({0.0, (double)(r + 1) * res - y0, (double)z[cell + W] - z0});
-  const V3 N = unit({0.0, (double)(r - 1) * res - y0, (double)z[cell - W] - z0});
-  const V3 E = unit({(double)(c + 1) * res - x0, 0.0, (double)z[cell + 1] - z0});
-  const V3 Wv = unit({(double)(c - 1) * res - x0, 0.0, (double)z[cell - 1] - z0});
-  const V3 n1 = unit(cross(E, N)), n2 = unit(cross(Wv, S)), n3 = unit(cross(N, Wv)), n4 = unit(cross(S, E));
-  const V3 n = unit({(((n1.x + n2.x) + n3.x) + n4.x) / 4.0, (((n1.y + n2.y) + n3.y) + n4.y) / 4.0,
-                     (((n1.z + n2.z) + n3.z) + n4.z) / 4.0});
+  const V3 n = normal_chain::cell_normal({0.0, (double)(r + 1) * res - y0, (double)z[cell + W] - z0},
+                                         {0.0, (double)(r - 1) * res - y0, (double)z[cell - W] - z0},
+                                         {(double)(c + 1) * res - x0, 0.0, (double)z[cell + 1] - z0},
+                                         {(double)(c - 1) * res - x0, 0.0, (double)z[cell - 1] - z0});
   o[0] = (float)n.x;
   o[1] = (float)n.y;
   o[2] = (float)n.z;

@@ -882,6 +882,99 @@ def grid_fill(src, near_row, rows=None, want_source=False, want_dist2=False):
     return dst, source, dist2, counts
 
 
+RAY_MAP_COUNTERS = ("std_sum", "std_count", "std_skipped", "bad_nr", "nr0", "nr_total")
+
+
+def _maps_f32(name, t, what, shape=None, contiguous=True):
+    """A float32 tensor of `shape` (None entries are free), or ValueError by name; the device is checked by _fill_device, last."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: {what} must be a tensor on the device (there is no host path)")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name}: {what} is {t.dtype}, not torch.float32")
+    if shape is not None and (t.dim() != len(shape) or any(w is not None and int(w) != int(h) for w, h in zip(shape, t.shape))):
+        raise ValueError(f"{name}: {what} {tuple(t.shape)} does not have the shape {tuple('*' if w is None else w for w in shape)}")
+    if contiguous and not t.is_contiguous():
+        raise ValueError(f"{name}: {what} {tuple(t.shape)} is not contiguous")
+    return t
+
+
+def ray_maps(z_vals, weights, depth, X=None, accumulate=False, normal_col=None, view=None, counters=None, want_surf=True):
+    """The per-ray reductions over the depth-sorted samples (bn_ray_maps).  z_vals, weights (R, S) and depth (R,) float32,
+    contiguous; X (R, S, E) float32 with any non-negative strides (a column slice of the field rows is read in place) or None;
+    normal_col: the first of three channels of X holding a normal, with view (R, 3) float32 = -rays_d (unit inner stride).
+    counters (6,) int64 is accumulated into when given (RAY_MAP_COUNTERS names its entries).
+    -> surf_idx (R,) int32, surf (R, E) or None, var (R,), std (R,), accum (R, E) or None, counters."""
+    name = "ray_maps"
+    _maps_f32(name, z_vals, "z_vals", (None, None))
+    R, S = z_vals.shape
+    _maps_f32(name, weights, "weights", (R, S))
+    _maps_f32(name, depth, "depth", (R,))
+    if not 1 <= S <= L.BN_MAPS_MAX_SAMPLES:
+        raise ValueError(f"{name}: S = {S} samples (1 to {L.BN_MAPS_MAX_SAMPLES})")
+    E = 0
+    if X is not None:
+        _maps_f32(name, X, "X", (R, S, None), contiguous=False)
+        E = X.shape[2]
+        if not 0 <= E <= L.BN_MAPS_MAX_CHANNELS:
+            raise ValueError(f"{name}: X has E = {E} channels (0 to {L.BN_MAPS_MAX_CHANNELS})")
+        if any(st < 0 for st in X.stride()):
+            raise ValueError(f"{name}: X has a negative stride {tuple(X.stride())}")
+    if accumulate and E == 0:
+        raise ValueError(f"{name}: accumulate=True needs a per-sample tensor X with at least one channel")
+    nc = -1
+    if normal_col is not None:
+        nc = int(normal_col)
+        if not 0 <= nc <= E - 3:
+            raise ValueError(f"{name}: normal column {nc} outside [0, E - 3] with E = {E}")
+        if view is None:
+            raise ValueError(f"{name}: a normal column needs the view vectors (view = -rays_d)")
+        _maps_f32(name, view, "view", (R, 3), contiguous=False)
+        if view.stride(1) != 1 or view.stride(0) < 0:
+            view = view.contiguous()
+    if counters is None:
+        counters = torch.zeros((len(RAY_MAP_COUNTERS),), dtype=torch.int64, device=z_vals.device)
+    if not (isinstance(counters, torch.Tensor) and counters.dtype == torch.int64 and counters.numel() == len(RAY_MAP_COUNTERS)
+            and counters.is_contiguous()):
+        raise ValueError(f"{name}: counters must be a contiguous int64 tensor of {len(RAY_MAP_COUNTERS)} entries")
+    _fill_device(name, z_vals, weights, depth, counters, *(t for t in (X, view if nc >= 0 else None) if t is not None))
+    dev = z_vals.device
+    surf_idx = torch.empty((R,), dtype=torch.int32, device=dev)
+    var, std = torch.empty((R,), dtype=torch.float32, device=dev), torch.empty((R,), dtype=torch.float32, device=dev)
+    surf = torch.empty((R, E), dtype=torch.float32, device=dev) if (E and want_surf) else None
+    accum = torch.empty((R, E), dtype=torch.float32, device=dev) if accumulate else None
+    raw = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    xr, xs, xc = (0, 0, 0) if (X is None or E == 0) else X.stride()
+    L.check(L.lib().bn_ray_maps(_p(z_vals), _p(weights), _p(depth), raw(X) if E else None, xr, xs, xc, nc, raw(view) if nc >= 0 else None,
+                                view.stride(0) if nc >= 0 else 0, R, S, E, _p(surf_idx), _p(surf), _p(var), _p(std), _p(accum),
+                                _p(counters), _stream()), "bn_ray_maps")
+    return surf_idx, surf, var, std, accum, counters
+
+
+def point_normals(points, valid=None, round_f32=True):
+    """The normals of an (H, W, 3) float64 image of points (bn_point_normals): -> normals (H, W, 3) float32, zero on the border, and
+    valid_out (H, W) float32 or None (with valid (H, W) float32).  round_f32: the reference's float32 points."""
+    name = "point_normals"
+    if not isinstance(points, torch.Tensor):
+        raise ValueError(f"{name}: points must be a tensor on the device (there is no host path)")
+    if points.dtype != torch.float64:
+        raise ValueError(f"{name}: points are {points.dtype}, not torch.float64 (point_cloud's output)")
+    if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] < 1 or points.shape[1] < 1:
+        raise ValueError(f"{name}: points {tuple(points.shape)} are not an (H, W, 3) image")
+    H, W = points.shape[0], points.shape[1]
+    if H * W > 1 << 30:
+        raise ValueError(f"{name}: image {H} x {W} (H W at most 2^30 cells)")
+    if valid is not None:
+        _maps_f32(name, valid, "valid", (H, W), contiguous=False)
+        valid = valid.contiguous()
+    _fill_device(name, points, *(() if valid is None else (valid,)))
+    points = points.contiguous()
+    out = torch.empty((H, W, 3), dtype=torch.float32, device=points.device)
+    valid_out = None if valid is None else torch.empty((H, W), dtype=torch.float32, device=points.device)
+    L.check(L.lib().bn_point_normals(_p(points), H, W, int(bool(round_f32)), _p(valid), _p(out), _p(valid_out), _stream()),
+            "bn_point_normals")
+    return out, valid_out
+
+
 def sample_shade_dirs(desc, X, w, rays_d, sun, view=None, rgb=None, brdf=None, want_brdf=False):
     """ray_shade_dirs for one BRDF per sample (bn_sample_shade_dirs), forward only.  X (R,S,C) depth-sorted field-output rows,
     w (R,S) their weights; rays_d (R,3) view with unit inner stride; sun (K,3); view (K,3) or None (-rays_d).  rgb / brdf: (K,R,3)

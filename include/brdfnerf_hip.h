@@ -639,6 +639,59 @@ int bn_dsm_shift_diff(const float *pred, const float *gt, int32_t H, int32_t W, 
 int bn_grid_nearest_col(const float *src, int32_t H, int32_t W, int32_t *near_row, void *stream);
 int bn_grid_fill(const float *src, const int32_t *near_row, int32_t H, int32_t W, int32_t row0, int32_t row1, float *dst, int32_t *source,
                  int32_t *dist2, long long *counts, void *stream);
+/* The validation maps of a rendered view (additive to ABI 7): what eval.py:403-456 and main.py:451-595 build from the per-sample
+ * dict of a whole view - the host np.argmin, the Python double loop of train_utils.get_surface_feature, calc_depth_std,
+ * visualize_accumulated_feature's sum, check_vec0, NormalRegLoss's percentage, calc_normal_from_pts3d - as reductions of one
+ * chunk of rays while it is on the device.
+ *
+ * bn_ray_maps.  z, w: float32 [R][S], the depth-sorted sample depths and their weights; depth: float32 [R].  X (nullable with
+ * E == 0): a per-sample float32 tensor of E channels, element (r, s, e) at X[r x_ray + s x_sample + e x_chan] (a column slice of
+ * the field rows is read in place).  normal_col: the first of three channels of X that hold a normal, or -1; view: float32, the
+ * view vector of ray r (-rays_d) at view[r view_stride + 0..2].  A NULL output is not computed.  Per ray r:
+ *   surf_idx int32 [R]   dev_s = fabsf(z_s - depth) in float32 (one rounding, then the sign cleared: torch.abs(z - depth)); the
+ *                        first s whose dev_s is NaN; without one the first s that attains the minimum.  That is np.argmin
+ *                        (eval.py:411-412) on every input, ties included.
+ *   surf float32 [R][E]  the 32 bits of X[r][surf_idx][e], copied without arithmetic (-0.0, denormals and NaN payloads keep
+ *                        their bits): get_surface_feature.
+ *   var, std float32 [R] v = 0.0 in float64; for s ascending t = (double)z_s - (double)depth, v = v + (t t) (double)w_s, every
+ *                        operation rounded on its own; var = (float)v, std = (float)sqrt(v): calc_depth_std_2, calc_depth_std.
+ *                        The order is serial per ray: the bits depend on no split.
+ *   accum float32 [R][E] a = 0.0 in float64; for s ascending a = a + (double)w_s (double)X[r][s][e] (the product of two float32
+ *                        values is exact in float64); accum = (float)a: the Accum=True rule of visualize_accumulated_feature.
+ * counters: int64 [6] the CALLER zeroes; integer adds only, one atomic per counter and block, so their values do not depend on
+ * the block order, on how the rays are chunked or on the number of devices that share a view:
+ *   [0] std_sum     += llrint((double)std 2^20) over the rays whose std is finite and below 2^40
+ *   [1] std_count   += those rays           [2] std_skipped += the other rays (NaN or inf: a NaN weight, a negative variance)
+ *   with a normal column n = X[r][s][normal_col + 0..2], per sample, in float64:
+ *   [3] bad_nr      += 1 where ((n.x v.x + n.y v.y) + n.z v.z) < 0, the products formed first (NormalRegLoss's perc_ng_nr; a NaN
+ *                      dot product is not counted, as `n_dot_v < 0` is false on it)
+ *   [4] nr0         += 1 where sqrt((n.x n.x + n.y n.y) + n.z n.z) > 0.99999 is FALSE (check_vec0; a NaN norm is counted, as
+ *                      torch.where(norm > 0.99999, 1, 0) gives 0 on it)
+ *   [5] nr_total    += S per ray
+ * The mean std of a view is counters[0] / (counters[1] 2^20), the percentages 100 counters[3 or 4] / counters[5].
+ * Refused (BN_EINVAL): NULL z, w, depth or counters; R < 0 or over 2^30; S < 1 or > BN_MAPS_MAX_SAMPLES; E outside [0, BN_MAPS_MAX_CHANNELS];
+ * E > 0 without X; surf or accum with E == 0; a normal column outside [0, E - 3] (other than -1) or without view; a negative
+ * stride.  R == 0 launches nothing.
+ *
+ * bn_point_normals: calc_normal_from_pts3d (sat_utils.py:16-50) for an image of points; bn_grid_normals is its special case
+ * P = (c resolution, r resolution, z) and shares the float64 chain per cell (its comment above states it).  points: float64
+ * [H][W][3].  round_f32 = 1: every coordinate is first rounded to float32 - the `.type(torch.FloatTensor)` of
+ * calc_normal_from_depth_v2 (datasets/satellite_rgb_dep.py:581), which at a UTM northing of 3.3e6 m quantises to 0.25 m - and
+ * the chain then runs in float64 on the rounded points; round_f32 = 0 is the exact reading.  The four neighbour vectors
+ * P(r + 1, c) - P, P(r - 1, c) - P, P(r, c + 1) - P, P(r, c - 1) - P are formed in float64, then as bn_grid_normals.  normals: float32
+ * [H][W][3], (0, 0, 0) on the border, NaN where a NaN coordinate is read.  The cross product is over the coordinate axis always:
+ * upstream's torch.cross without dim takes the FIRST axis of size 3 and so goes wrong when H - 2 == 3 or W - 2 == 3; that quirk
+ * is not reproduced.  valid_in float32 [H][W] with valid_out float32 [H][W] (both or neither), the rule of :19-24 in float32:
+ * valid_out = valid_in where valid_in < 1e-5f, else 1; an interior cell instead ((v(r + 1, c) v(r - 1, c)) v(r, c + 1)) v(r, c - 1).
+ * Refused (BN_EINVAL): NULL points or normals, H or W < 1, H W over 2^30, round_f32 other than 0 or 1, one of valid_in /
+ * valid_out without the other. */
+#define BN_MAPS_MAX_SAMPLES 4096
+#define BN_MAPS_MAX_CHANNELS 64
+int bn_ray_maps(const float *z, const float *w, const float *depth, const float *X, int64_t x_ray, int64_t x_sample, int64_t x_chan,
+                int32_t normal_col, const float *view, int64_t view_stride, int64_t R, int32_t S, int32_t E, int32_t *surf_idx,
+                float *surf, float *var, float *std, float *accum, long long *counters, void *stream);
+int bn_point_normals(const double *points, int32_t H, int32_t W, int32_t round_f32, const float *valid_in, float *normals,
+                     float *valid_out, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
