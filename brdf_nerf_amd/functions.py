@@ -488,7 +488,9 @@ def set_adam_steps(state, steps, betas=(0.9, 0.999)):
     """Write the per-group optimiser step counts (and the beta powers that go with them) into a step state."""
     steps = list(steps) + [0] * (4 - len(steps))
     state.view(torch.int32)[6:10] = torch.tensor(steps, dtype=torch.int32)
-    pw = [float(betas[0]) ** s for s in steps] + [float(betas[1]) ** s for s in steps]
+    # the powers of the betas as the kernels receive them (C `float` arguments), as bn_adam_multi's running products hold them
+    b1, b2 = (float(torch.tensor(float(b), dtype=torch.float32)) for b in betas)
+    pw = [b1 ** s for s in steps] + [b2 ** s for s in steps]
     state.view(torch.float64)[L.BN_STATE_POW_OFF // 8:L.BN_STATE_POW_OFF // 8 + 8] = torch.tensor(pw, dtype=torch.float64)
 
 

@@ -292,6 +292,10 @@ int bn_brdf_microfacet_backward(const float *l, const float *v, const float *n, 
  * Training-step tail (main.py:147-168 Adam; metrics.py:39-61 MSE): fused Adam over one flat fp32
  * parameter buffer (the nn.Parameters are views into it).
  * ------------------------------------------------------------------------------------------- */
+/* The betas of bn_adam_step / bn_adam_multi are the float32 values the arguments hold, promoted to double wherever a power
+ * is taken: beta^step is ((double)beta)^step (bn_adam_step: pow; bn_adam_multi: a running product in the step state), and
+ * 1.f - beta is exact in float32.  A caller that writes the state's powers itself (resume) takes powers of the same
+ * float32 values: for beta2 = 0.999 (0.99900001287 in float32) the double's power is 1.3e-5 away after 1000 steps. */
 int bn_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
                  float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale,
                  void *stream);
@@ -750,7 +754,8 @@ int bn_unfold_heads(const bn_fold_desc *d, void *stream);
  * group g = elements [lo[g], hi[g]) (multiples of 4), stepped only when active[g] (a group that is not in this step's graph
  * has grad None upstream and is skipped).  Step counts, the learning rate and the draw counter live in `state`
  * (bn_step_state): the kernel uses adam_step[g] + 1 and, when its last workgroup finishes, increments the active groups'
- * counts and rng_step and folds the loss partials into the loss ring.  zero_grad != 0: the gradient elements it read are set to 0. */
+ * counts and rng_step and folds the loss partials into the loss ring.  zero_grad != 0: the gradient elements it read are set to 0.
+ * beta1, beta2: see bn_adam_step - the state's beta1_pow / beta2_pow are powers of the float32 values. */
 int bn_adam_multi(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int32_t n_groups, const int64_t *lo,
                   const int64_t *hi, const int32_t *active, float beta1, float beta2, float eps, float weight_decay,
                   float grad_scale, int32_t zero_grad, void *state, void *stream);
