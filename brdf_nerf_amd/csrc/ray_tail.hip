@@ -14,6 +14,7 @@
 #pragma clang fp contract(off)
 #include "brdf_eval.h"
 #include "shade_row.h"
+#include "composite_ray.h"
 
 namespace {
 
@@ -22,14 +23,14 @@ struct ShadeArgs {
   const float *acc, *wsum, *depth, *var;
   const float *rays_d, *sun_d;           // sun_d nullptr: (1, 1, 1) (the non-satellite data sets, rendering.py:190)
   int64_t rd_stride, sd_stride;
-  const float *rgbs, *valid, *tdepth, *tweight, *tstd;
-  int64_t v_stride, td_stride, tw_stride, ts_stride;
+  const float *rgbs;
+  DepthPrior prior;
   int64_t R;
   float *rgb, *ray_loss, *loss_acc;
-  int loss_slots;
+  int loss_slots;                       // report_ray_loss (composite_ray.h)
   float *d_acc, *d_wsum, *d_depth;
   const float *extra_loss;              // nullable: per-ray loss terms computed elsewhere (NormalRegLoss of the compositing kernel)
-  unsigned long long *nonfinite;        // nullable: a ray whose loss term is not finite contributes nothing (loss 0, gradients 0) and is counted
+  unsigned long long *nonfinite;        // nullable: report_ray_loss
 };
 
 // KIND: BN_SHADE_LAMBERT / RPV / HAPKE / MICROFACET.  Dual slots (shade_row.h): the normal and albedo slots are seeded at the
@@ -76,33 +77,18 @@ template <int KIND> __global__ __launch_bounds__(64) void ray_shade_loss_kernel(
     db[c] = dy * irr;
     if (A.rgb) A.rgb[ray * 3 + c] = y;
   }
-  float dd = 0.f, dws = 0.f;
-  if (A.tdepth && A.valid[ray * A.v_stride] > 0.f) {          // DepthLoss (metrics.py:82-161), as bn_lambert_tail
-    const float td = A.tdepth[ray * A.td_stride], tw = A.tweight[ray * A.tw_stride], ts = A.tstd[ray * A.ts_stride];
-    const float var = A.var ? A.var[ray] : 0.f;
-    const bool apply = q.usealldepth || (fabsf(depth - td) - ts > 0.f) || (ts < sqrtf(var));
-    if (apply) {
-      const float k = q.lambda_ds / 3.f / (float)A.R;
-      loss += k * tw * (depth - td) * (depth - td);
-      dd = k * 2.f * tw * (depth - td);
-    }
-  }
+  float dd, dws = 0.f;
+  const float var = A.var ? A.var[ray] : 0.f;
+  depth_loss(A.prior, ray, depth, var, q.lambda_ds, q.usealldepth, A.R, loss, dd);
   if (q.lambda_hs > 0.f) {
     // HardSurfaceLoss: lambda/R * sum_s w_s (z_s - depth)^2; the per-sample part of its gradient, lambda/R (z_s - depth)^2,
     // is added by the composite backward (hs_scale); d/d depth = -2 lambda/R (sum_s w_s z_s - depth sum_s w_s)
     const float k = q.lambda_hs / (float)A.R;
-    loss += k * (A.var ? A.var[ray] : 0.f);
+    loss += k * var;
     dd += -2.f * k * (depth - depth * ws);
   }
-  // A ray whose shaded value is NaN / Inf (a BRDF evaluated at a singular geometry that the reference's check_nan replacements
-  // do not cover) makes the reference's loss NaN and its whole gradient with it.  With `nonfinite` (FusedTrainer.sanitize_grads)
-  // such a ray is left out of the step - loss term 0, gradients 0 - and counted, like the non-finite gradient elements the
-  // composite backward drops.
   if (A.extra_loss) loss += A.extra_loss[ray];
-  const bool drop = A.nonfinite && !(fabsf(loss) <= 3.0e38f);
-  if (drop) { atomicAdd(A.nonfinite + (isnan(loss) ? 0 : 1), 1ull); loss = 0.f; }
-  if (A.ray_loss) A.ray_loss[ray] = loss;
-  if (A.loss_acc) atomicAdd(A.loss_acc + (int)(ray % A.loss_slots), loss);
+  const bool drop = report_ray_loss(true, ray, loss, A.nonfinite, A.ray_loss, A.loss_acc, A.loss_slots);
   // J^T: slots -> composited sums
   float *da = A.d_acc + ray * C;
   for (int c = 0; c < C; ++c) da[c] = 0.f;
@@ -129,12 +115,12 @@ extern "C" int bn_ray_shade_loss(const bn_shade_desc *desc, const float *acc, co
   BN_REQUIRE(desc && acc && wsum && depth && rgbs && d_acc && d_wsum && d_depth && R > 0, "ray_shade_loss: null argument");
   const bn_shade_desc &q = *desc;
   if (int e = shade_desc_check(q, rays_d != nullptr, "ray_shade_loss")) return e;
-  BN_REQUIRE(!target_depth || (valid_depth && target_weight && target_std && var), "ray_shade_loss: incomplete depth prior");
-  BN_REQUIRE(!(q.lambda_hs > 0.f) || var, "ray_shade_loss: lambda_hs needs the per-ray variance");
   ShadeArgs a;
+  a.prior = DepthPrior{valid_depth, target_depth, target_weight, target_std, v_stride, td_stride, tw_stride, ts_stride};
+  if (int e = depth_prior_check(a.prior, var != nullptr, "ray_shade_loss")) return e;
+  BN_REQUIRE(!(q.lambda_hs > 0.f) || var, "ray_shade_loss: lambda_hs needs the per-ray variance");
   a.d = q; a.acc = acc; a.wsum = wsum; a.depth = depth; a.var = var; a.rays_d = rays_d; a.sun_d = sun_d; a.rd_stride = rd_stride;
-  a.sd_stride = sd_stride; a.rgbs = rgbs; a.valid = valid_depth; a.tdepth = target_depth; a.tweight = target_weight; a.tstd = target_std;
-  a.v_stride = v_stride; a.td_stride = td_stride; a.tw_stride = tw_stride; a.ts_stride = ts_stride; a.R = R; a.rgb = rgb;
+  a.sd_stride = sd_stride; a.rgbs = rgbs; a.R = R; a.rgb = rgb;
   a.ray_loss = ray_loss; a.loss_acc = loss_acc; a.loss_slots = loss_slots > 0 ? loss_slots : 1; a.d_acc = d_acc; a.d_wsum = d_wsum;
   a.d_depth = d_depth; a.nonfinite = nonfinite; a.extra_loss = extra_loss;
   const dim3 grid((unsigned)ceil_div64(R, 64));

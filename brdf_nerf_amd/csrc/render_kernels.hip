@@ -6,14 +6,9 @@
 // reference's separate ATen ops (needed for bit-exact sample indices).
 #include "common.h"
 #pragma clang fp contract(off)
+#include "composite_ray.h"
 
 #define WAVES_PER_BLOCK 4
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // torch.linspace(start, end, steps)[i] in fp32 (symmetric formula of ATen's RangeFactories).
 __device__ __forceinline__ float linspace_at(float start, float end, int steps, int i) {
@@ -141,10 +136,7 @@ extern "C" int bn_rng_uniform(const unsigned long long *rng, uint32_t rng_stream
 }
 
 // ------------------------------------------------------------------------------------------ compositing
-// Lane i of the ray's wave owns samples [i*c, (i+1)*c), c = ceil(S/64) <= BN_MAX_C: the exclusive prefix product
-// of (1 - alpha + 1e-10) is a per-lane serial product + a 6-step wavefront shuffle scan.
-#define BN_MAX_CPL 8   // samples per lane -> S <= 512
-
+// The recurrence, the lane-owned front of a ray (RayFront) and its backward sweep: composite_ray.h.
 struct CompArgs {
   const float *z, *sigma, *noise, *chan;
   int64_t sigma_stride, chan_stride;
@@ -245,36 +237,9 @@ template <int LG, bool VEC> __device__ __forceinline__ void comp_flat_bwd_store(
       else FN<3, false>(__VA_ARGS__);                                             \
     }                                                                             \
   } while (0)
-__device__ __forceinline__ void lds_wave_sync() {   // LDS hand-over inside one wave: its DS operations execute in order
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
 
-__device__ __forceinline__ float wave_excl_prod(float v, int lane) {
-  // inclusive Hillis-Steele scan, then shift by one lane
-  float p = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const float t = __shfl_up(p, o);
-    if (lane >= o) p *= t;
-  }
-  const float e = __shfl_up(p, 1);
-  return lane == 0 ? 1.f : e;
-}
-__device__ __forceinline__ float wave_excl_sum_rev(float v, int lane) {
-  // exclusive suffix sum: sum of v over lanes > lane
-  float p = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const float t = __shfl_down(p, o);
-    if (lane + o < 64) p += t;
-  }
-  const float e = __shfl_down(p, 1);
-  return lane == 63 ? 0.f : e;
-}
-
-template <bool BWD> __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void composite_kernel(const CompArgs A) {
+// (second launch bound: the backward's LDS admits 6 waves per SIMD - its registers are held to that)
+template <bool BWD> __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, BWD ? 6 : 8) void composite_kernel(const CompArgs A) {
   __shared__ float lds_w[WAVES_PER_BLOCK][64 * BN_MAX_CPL];                 // per-wave slices: weights,
   __shared__ float lds_g[BWD ? WAVES_PER_BLOCK : 1][BWD ? 64 * BN_MAX_CPL : 1];   // sum_c d_acc[c] chan[s][c],
   __shared__ float lds_d[BWD ? WAVES_PER_BLOCK : 1][BWD ? 64 * BN_MAX_CPL : 1];   // d sigma
@@ -283,114 +248,57 @@ template <bool BWD> __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void comp
   if (ray >= A.R) return;
   float *wl = lds_w[wv], *gs = lds_g[BWD ? wv : 0], *dsl = lds_d[BWD ? wv : 0];
   const bool flat = A.flat_lg >= 0;
-  const int S = A.S, cpl = (S + 63) / 64;
-  const float *z = A.z + ray * S;
-  float zv[BN_MAX_CPL], al[BN_MAX_CPL], u[BN_MAX_CPL], dad[BN_MAX_CPL];  // dad = d alpha / d sigma
-  float lp = 1.f;
-#pragma unroll
-  for (int j = 0; j < BN_MAX_CPL; ++j) {
-    zv[j] = 0.f; al[j] = 0.f; u[j] = 1.f; dad[j] = 0.f;
-    const int s = lane * cpl + j;
-    if (j < cpl && s < S) {
-      zv[j] = z[s];
-      const float delta = s == S - 1 ? 1e10f : z[s + 1] - zv[j];
-      float sg = A.sigma[(ray * S + s) * A.sigma_stride];
-      if (A.noise) sg = sg + A.noise[ray * S + s] * A.noise_std;
-      const float rs = sg > 0.f ? sg : 0.f;
-      const float e = expf(-delta * rs);
-      al[j] = 1.f - e;
-      u[j] = 1.f - al[j] + 1e-10f;
-      dad[j] = sg > 0.f ? delta * e : 0.f;
-      lp *= u[j];
-    }
-  }
-  float T = wave_excl_prod(lp, lane);  // transparency before this lane's first sample
-  float tr[BN_MAX_CPL], w[BN_MAX_CPL];
-#pragma unroll
-  for (int j = 0; j < BN_MAX_CPL; ++j) {
-    tr[j] = T;
-    w[j] = al[j] * T;
-    T *= u[j];
-  }
+  const int S = A.S;
+  RayFront F(S, lane);
+  F.load(A.z + ray * S, [&](int, int s) {
+    float sg = A.sigma[(ray * S + s) * A.sigma_stride];
+    if (A.noise) sg = sg + A.noise[ray * S + s] * A.noise_std;
+    return sg;
+  });
   if (!BWD) {
-    float dsum = 0.f;
-#pragma unroll
-    for (int j = 0; j < BN_MAX_CPL; ++j) {
-      const int s = lane * cpl + j;
-      if (j < cpl && s < S) {
-        const int64_t o = ray * S + s;
-        if (A.alphas) A.alphas[o] = al[j];
-        if (A.trans) A.trans[o] = tr[j];
-        if (A.weights) A.weights[o] = w[j];
-        dsum += w[j] * zv[j];
-      }
-    }
-    dsum = wave_sum(dsum);
+    float dsum, ws;
+    F.store(ray * S, A.alphas, A.trans, A.weights, dsum, ws);
     if (lane == 0 && A.depth) A.depth[ray] = dsum;
     if (flat) {
-#pragma unroll
-      for (int j = 0; j < BN_MAX_CPL; ++j) {
-        const int s = lane * cpl + j;
-        if (j < cpl && s < S) wl[s] = w[j];
-      }
+      F.weights_to(wl);
       lds_wave_sync();
       BN_COMP_FLAT(comp_flat_fwd, A, ray, lane, wl);
     } else if (A.chan && A.acc) {
       for (int c = 0; c < A.C; ++c) {
         float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < BN_MAX_CPL; ++j) {
-          const int s = lane * cpl + j;
-          if (j < cpl && s < S) a += w[j] * A.chan[(ray * S + s) * A.chan_stride + c];
-        }
+        BN_RAY_EACH(F, j, s) { a += F.w[j] * A.chan[(ray * S + s) * A.chan_stride + c]; }
         a = wave_sum(a);
         if (lane == 0) A.acc[ray * A.C + c] = a;
       }
     }
   } else {
-    // g_s = dL/dw_s; dL/dalpha_s = g_s T_s - (1/u_s) sum_{k>s} g_k w_k   
     const float dd = A.d_depth ? A.d_depth[ray] : 0.f;
     if (flat) {
-#pragma unroll
-      for (int j = 0; j < BN_MAX_CPL; ++j) {
-        const int s = lane * cpl + j;
-        if (j < cpl && s < S) wl[s] = w[j];
-      }
+      F.weights_to(wl);
       BN_COMP_FLAT(comp_flat_bwd_dot, A, ray, lane, gs);
       lds_wave_sync();
     }
-    float g[BN_MAX_CPL], gw = 0.f;
-#pragma unroll
-    for (int j = 0; j < BN_MAX_CPL; ++j) {
-      g[j] = 0.f;
-      const int s = lane * cpl + j;
-      if (j < cpl && s < S) {
-        float gg = dd * zv[j];
-        if (A.d_weights) gg += A.d_weights[ray * S + s];
-        if (flat) gg += gs[s];
-        else if (A.chan && A.d_acc) {
-          const float *ch = A.chan + (ray * S + s) * A.chan_stride;
-          float *dch = A.d_chan ? A.d_chan + (ray * S + s) * A.d_chan_stride : nullptr;
-          for (int c = 0; c < A.C; ++c) {          // (generic strided rows only: the dense layout takes the flat path)
-            const float dc = A.d_acc[ray * A.C + c];
-            gg += dc * ch[c];
-            if (dch) dch[c] = w[j] * dc;
-          }
+    float g[BN_MAX_CPL] = {}, gw = 0.f;      // g_s = dL/dw_s
+    BN_RAY_EACH(F, j, s) {
+      float gg = dd * F.zv[j];
+      if (A.d_weights) gg += A.d_weights[ray * S + s];
+      if (flat) gg += gs[s];
+      else if (A.chan && A.d_acc) {
+        const float *ch = A.chan + (ray * S + s) * A.chan_stride;
+        float *dch = A.d_chan ? A.d_chan + (ray * S + s) * A.d_chan_stride : nullptr;
+        for (int c = 0; c < A.C; ++c) {          // (generic strided rows only: the dense layout takes the flat path)
+          const float dc = A.d_acc[ray * A.C + c];
+          gg += dc * ch[c];
+          if (dch) dch[c] = F.w[j] * dc;
         }
-        g[j] = gg;
-        gw += gg * w[j];
       }
+      g[j] = gg;
+      gw += gg * F.w[j];
     }
-    float suffix = wave_excl_sum_rev(gw, lane);  // sum of g*w over later lanes
-#pragma unroll
-    for (int j = BN_MAX_CPL - 1; j >= 0; --j) {
-      const int s = lane * cpl + j;
-      if (j < cpl && s < S) {
-        const float dalpha = g[j] * tr[j] - suffix / u[j];
-        if (flat && A.fused_dsigma) dsl[s] = dalpha * dad[j];
-        else A.d_sigma[(ray * S + s) * A.d_sigma_stride] = dalpha * dad[j];
-        suffix += g[j] * w[j];
-      }
+    F.backward(g, gw);      // g[j]: now dL/dsigma_s
+    BN_RAY_EACH(F, j, s) {
+      if (flat && A.fused_dsigma) dsl[s] = g[j];
+      else A.d_sigma[(ray * S + s) * A.d_sigma_stride] = g[j];
     }
     if (flat && A.d_chan) {
       lds_wave_sync();
@@ -459,7 +367,8 @@ extern "C" int bn_composite_backward(const float *z, const float *sigma, int64_t
 // (metrics.py:82-161, subset rule as a mask), and their gradients w.r.t. the composited sums, the depth and the weights -
 // what ~60 small ATen launches (forward + autograd) compute otherwise.  One wavefront per ray.
 struct LossArgs {
-  const float *acc, *weights, *z, *depth, *rgbs, *valid, *tdepth, *tweight, *tstd;
+  const float *acc, *weights, *z, *depth, *rgbs;
+  DepthPrior prior;
   float *ray_loss, *rgb, *d_acc, *d_depth, *d_weights;
   int64_t R;
   int C, S, usealldepth;
@@ -492,16 +401,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void lambert_loss_kernel(cons
     dws -= dy * A.pad;
     if (lane == 0) A.rgb[ray * 3 + c] = y;
   }
-  float dd = 0.f;
-  if (A.tdepth && A.valid[ray] > 0.f) {
-    const float td = A.tdepth[ray], tw = A.tweight[ray], ts = A.tstd[ray];
-    const bool apply = A.usealldepth || (fabsf(d - td) - ts > 0.f) || (ts < sqrtf(var));
-    if (apply) {
-      const float k = A.lambda_ds / 3.f / (float)A.R;
-      loss += k * tw * (d - td) * (d - td);
-      dd = k * 2.f * tw * (d - td);
-    }
-  }
+  float dd;
+  depth_loss(A.prior, ray, d, var, A.lambda_ds, A.usealldepth, A.R, loss, dd);
   if (lane == 0) {
     A.ray_loss[ray] = loss;
     A.d_depth[ray] = dd;
@@ -517,10 +418,10 @@ extern "C" int bn_lambert_loss(const float *acc, int32_t C, const float *weights
                                float *d_depth, float *d_weights, void *stream) {
   BN_REQUIRE(acc && weights && z && depth && rgbs && ray_loss && rgb && d_acc && d_depth && d_weights && R > 0 && S >= 1 && C >= 3,
              "lambert_loss: bad arguments");
-  BN_REQUIRE(!target_depth || (valid_depth && target_weight && target_std), "lambert_loss: incomplete depth prior");
   LossArgs a;
-  a.acc = acc; a.weights = weights; a.z = z; a.depth = depth; a.rgbs = rgbs; a.valid = valid_depth; a.tdepth = target_depth;
-  a.tweight = target_weight; a.tstd = target_std; a.ray_loss = ray_loss; a.rgb = rgb; a.d_acc = d_acc; a.d_depth = d_depth;
+  a.prior = DepthPrior{valid_depth, target_depth, target_weight, target_std, 1, 1, 1, 1};
+  if (int e = depth_prior_check(a.prior, true, "lambert_loss")) return e;
+  a.acc = acc; a.weights = weights; a.z = z; a.depth = depth; a.rgbs = rgbs; a.ray_loss = ray_loss; a.rgb = rgb; a.d_acc = d_acc; a.d_depth = d_depth;
   a.d_weights = d_weights; a.R = R; a.C = C; a.S = S; a.usealldepth = usealldepth; a.pad = rgb_padding;
   a.lambda_rgb = lambda_rgb; a.lambda_ds = lambda_ds;
   lambert_loss_kernel<<<dim3((unsigned)ceil_div64(R, WAVES_PER_BLOCK)), 64 * WAVES_PER_BLOCK, 0, (hipStream_t)stream>>>(a);
@@ -713,39 +614,14 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void composite_guided_kernel(
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t ray = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wv;
   if (ray >= A.g.R) return;
-  const int S = A.g.S, cpl = (S + 63) / 64;
+  const int S = A.g.S;
   const float *z = A.g.z + ray * S;
-  float zv[BN_MAX_CPL], al[BN_MAX_CPL], u[BN_MAX_CPL];
-  float lp = 1.f;
-#pragma unroll
-  for (int j = 0; j < BN_MAX_CPL; ++j) {
-    zv[j] = 0.f; al[j] = 0.f; u[j] = 1.f;
-    const int s = lane * cpl + j;
-    if (j < cpl && s < S) {
-      zv[j] = z[s];
-      const float delta = s == S - 1 ? 1e10f : z[s + 1] - zv[j];
-      const float sg = noised(A.noise, A.sigma[(ray * S + s) * A.sigma_stride], ray, S, s);
-      const float rs = sg > 0.f ? sg : 0.f;
-      al[j] = 1.f - expf(-delta * rs);
-      u[j] = 1.f - al[j] + 1e-10f;
-      lp *= u[j];
-    }
-  }
-  float T = wave_excl_prod(lp, lane);
-  float dsum = 0.f;
+  RayFront F(S, lane);
+  F.load(z, [&](int, int s) { return noised(A.noise, A.sigma[(ray * S + s) * A.sigma_stride], ray, S, s); });
+  float dsum, ws;
   float *wl = s_w[wv];
-#pragma unroll
-  for (int j = 0; j < BN_MAX_CPL; ++j) {
-    const int s = lane * cpl + j;
-    if (j < cpl && s < S) {
-      const float w = al[j] * T;
-      wl[s] = w;
-      if (A.weights) A.weights[ray * S + s] = w;
-      dsum += w * zv[j];
-    }
-    T *= u[j];
-  }
-  dsum = wave_sum(dsum);
+  F.store(ray * S, nullptr, nullptr, A.weights, dsum, ws);
+  F.weights_to(wl);
   if (lane == 0 && A.depth) A.depth[ray] = dsum;
   lds_wave_sync();
   guided_ray(A.g, ray, lane, z, wl, dsum, s_edges[wv], s_cdf[wv], s_key[wv], s_idx[wv]);
@@ -822,12 +698,12 @@ struct MergedArgs {
   int64_t R;
   float *alphas, *trans, *weights, *depth, *acc, *wsum, *var;
   // MODE 1
-  const float *rgbs, *valid, *tdepth, *tweight, *tstd;
-  int64_t v_stride, td_stride, tw_stride, ts_stride;
+  const float *rgbs;
+  DepthPrior prior;
   float pad, lambda_rgb, lambda_ds;
   int usealldepth;
   float *ray_loss, *rgb, *loss_acc;
-  int loss_slots;                  // the rays' loss terms are added to loss_acc[ray % loss_slots] (spread: same-address atomics serialise)
+  int loss_slots;                  // report_ray_loss (composite_ray.h)
   // MODE 2
   const float *d_weights, *d_depth, *d_acc, *d_wsum, *depth_in;
   float hs_scale;
@@ -840,67 +716,44 @@ struct MergedArgs {
   NoiseArgs noise;                 // --noise_std on the merged set (position = sorted position)
 };
 
+// NormalRegLoss, the per-sample term of normal field f (0: analytic, 1: learned): nv = min(0, n . view), n = channels c0 .. c0 + 2
+// of the row at(c), and the field's lambda.  false: the field is off (no channel or lambda <= 0); lam and nv are left alone.
+template <typename At> __device__ __forceinline__ bool nreg_term(const bn_normal_reg &n, int f, float vx, float vy, float vz, At &&at,
+                                                                 float &lam, float &nv) {
+  const int c0 = f == 0 ? n.ch_an : n.ch_lr;
+  const float l = f == 0 ? n.lambda_an : n.lambda_lr;
+  if (c0 < 0 || !(l > 0.f)) return false;
+  lam = l;
+  nv = fminf(at(c0) * vx + at(c0 + 1) * vy + at(c0 + 2) * vz, 0.f);
+  return true;
+}
+
 // C4 (C == 4 and 16-byte aligned blocks: the Lambertian model): a sample's row is ONE 16-byte load kept in registers for the
 // forward sums and the backward dot products, and one 16-byte store of its gradient row.
 template <int MODE, bool C4> __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void merged_composite_kernel(const MergedArgs A) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t ray = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wv;
   if (ray >= A.R) return;
-  const int S = A.S2, C = A.C, cpl = (S + 63) / 64, S1 = A.S1, Sg = S - S1;
-  const float *z = A.z + ray * S;
-  float zv[BN_MAX_CPL], al[BN_MAX_CPL], u[BN_MAX_CPL], dad[BN_MAX_CPL];
-  int64_t roff[BN_MAX_CPL];      // element offset of the sample's row; >= 0: in out1, < 0: ~offset in out2
-  f32x4 rv[C4 ? BN_MAX_CPL : 1];
-  float lp = 1.f;
+  const int S = A.S2, C = A.C, S1 = A.S1, Sg = S - S1;
+  int64_t roff[BN_MAX_CPL] = {};      // element offset of the sample's row; >= 0: in out1, < 0: ~offset in out2
+  f32x4 rv[C4 ? BN_MAX_CPL : 1] = {};
   auto rowp = [&](int64_t o) { return o >= 0 ? A.out1 + o : A.out2 + ~o; };
   auto chan = [&](int j, int c) { return C4 ? rv[C4 ? j : 0][c] : rowp(roff[j])[c]; };
-#pragma unroll
-  for (int j = 0; j < BN_MAX_CPL; ++j) {
-    zv[j] = 0.f; al[j] = 0.f; u[j] = 1.f; dad[j] = 0.f; roff[j] = 0;
-    const int s = lane * cpl + j;
-    if (j < cpl && s < S) {
-      const int64_t i = A.idx ? A.idx[ray * S + s] : (int64_t)s;
-      roff[j] = i < S1 ? (ray * S1 + i) * C : ~((ray * Sg + (i - S1)) * C);
-      zv[j] = z[s];
-      const float delta = s == S - 1 ? 1e10f : z[s + 1] - zv[j];
-      if (C4) rv[C4 ? j : 0] = *(const f32x4 *)rowp(roff[j]);
-      const float sg = noised(A.noise, chan(j, 3), ray, S, s);
-      const float rs = sg > 0.f ? sg : 0.f;
-      const float e = expf(-delta * rs);
-      al[j] = 1.f - e;
-      u[j] = 1.f - al[j] + 1e-10f;
-      dad[j] = sg > 0.f ? delta * e : 0.f;
-      lp *= u[j];
-    } else if (C4) {
-      rv[C4 ? j : 0] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
-  float T = wave_excl_prod(lp, lane);
-  float tr[BN_MAX_CPL], w[BN_MAX_CPL];
-#pragma unroll
-  for (int j = 0; j < BN_MAX_CPL; ++j) {
-    tr[j] = T;
-    w[j] = al[j] * T;
-    T *= u[j];
-  }
+  RayFront F(S, lane);
+  F.load(A.z + ray * S, [&](int j, int s) {
+    const int64_t i = A.idx ? A.idx[ray * S + s] : (int64_t)s;
+    roff[j] = i < S1 ? (ray * S1 + i) * C : ~((ray * Sg + (i - S1)) * C);
+    if (C4) rv[C4 ? j : 0] = *(const f32x4 *)rowp(roff[j]);
+    return noised(A.noise, chan(j, 3), ray, S, s);
+  });
+  const bool nreg_on = MODE == 0 ? (A.nreg.rays_d && A.reg_out) : (MODE == 2 && A.nreg.rays_d != nullptr);
+  float vx = 0.f, vy = 0.f, vz = 0.f;      // view = -rays_d
+  if (nreg_on) { const float *rd = A.nreg.rays_d + ray * A.nreg.rd_stride; vx = -rd[0]; vy = -rd[1]; vz = -rd[2]; }
   float dd = 0.f, dws = 0.f;         // d loss / d depth, d loss / d (sum_s w_s)
   float dacc[BN_MAX_CH];             // MODE 1: channels 0..2 only
   if (MODE != 2) {
-    float dsum = 0.f, ws = 0.f;
-#pragma unroll
-    for (int j = 0; j < BN_MAX_CPL; ++j) {
-      const int s = lane * cpl + j;
-      if (j < cpl && s < S) {
-        const int64_t o = ray * S + s;
-        if (A.alphas) A.alphas[o] = al[j];
-        if (A.trans) A.trans[o] = tr[j];
-        if (A.weights) A.weights[o] = w[j];
-        dsum += w[j] * zv[j];
-        ws += w[j];
-      }
-    }
-    dsum = wave_sum(dsum);
-    ws = wave_sum(ws);
+    float dsum, ws;
+    F.store(ray * S, A.alphas, A.trans, A.weights, dsum, ws);
     if (lane == 0 && A.depth) A.depth[ray] = dsum;
     if (lane == 0 && A.wsum) A.wsum[ray] = ws;
     const int nacc = MODE == 1 ? 3 : C;
@@ -908,37 +761,23 @@ template <int MODE, bool C4> __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) 
     if (MODE == 1 || A.acc) {
       for (int c = 0; c < nacc; ++c) {
         float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < BN_MAX_CPL; ++j) {
-          const int s = lane * cpl + j;
-          if (j < cpl && s < S) a += w[j] * chan(j, c);
-        }
+        BN_RAY_EACH(F, j, s) { a += F.w[j] * chan(j, c); }
         a = wave_sum(a);
         if (lane == 0 && A.acc) A.acc[ray * C + c] = a;
         if (MODE == 1 && c < 3) a3[c] = a;
       }
       if (MODE == 1 && A.acc && lane == 0) A.acc[ray * C + 3] = 0.f;
     }
-    if (MODE == 0 && A.nreg.rays_d && A.reg_out) {
-      const float *rd = A.nreg.rays_d + ray * A.nreg.rd_stride;
-      const float vx = -rd[0], vy = -rd[1], vz = -rd[2];
+    if (MODE == 0 && nreg_on) {
       float reg = 0.f;
 #pragma unroll
       for (int f = 0; f < 2; ++f) {
-        const int c0 = f == 0 ? A.nreg.ch_an : A.nreg.ch_lr;
-        const float lam = f == 0 ? A.nreg.lambda_an : A.nreg.lambda_lr;
-        if (c0 < 0 || !(lam > 0.f)) continue;
-        float part = 0.f;
-#pragma unroll
-        for (int j = 0; j < BN_MAX_CPL; ++j) {
-          const int s = lane * cpl + j;
-          if (j < cpl && s < S) {
-            const float *row = rowp(roff[j]);
-            const float nv = fminf(row[c0] * vx + row[c0 + 1] * vy + row[c0 + 2] * vz, 0.f);
-            part += w[j] * nv * nv;
-          }
+        float part = 0.f, lam = 0.f, nv;      // lam stays 0 where the field is off
+        BN_RAY_EACH(F, j, s) {
+          const float *row = rowp(roff[j]);
+          if (nreg_term(A.nreg, f, vx, vy, vz, [&](int c) { return row[c]; }, lam, nv)) part += F.w[j] * nv * nv;
         }
-        reg += lam * part;
+        if (lam > 0.f) reg += lam * part;
       }
       reg = wave_sum(reg);
       if (lane == 0) A.reg_out[ray] = reg;
@@ -946,25 +785,17 @@ template <int MODE, bool C4> __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) 
     if (MODE == 0 && A.nreg.lambda_spv != 0.f && A.nreg.spv_ray) {     // NormalLoss 'an_lr': this ray's (sum w, sum |n_an - n_lr|)
       const int ca = A.nreg.spv_ch_an, cl = A.nreg.spv_ch_lr;
       float sw = 0.f, sd = 0.f;
-#pragma unroll
-      for (int j = 0; j < BN_MAX_CPL; ++j) {
-        const int s = lane * cpl + j;
-        if (j < cpl && s < S) {
-          const float *row = rowp(roff[j]);
-          sw += w[j];
-          sd += fabsf(row[ca] - row[cl]) + fabsf(row[ca + 1] - row[cl + 1]) + fabsf(row[ca + 2] - row[cl + 2]);
-        }
+      BN_RAY_EACH(F, j, s) {
+        const float *row = rowp(roff[j]);
+        sw += F.w[j];
+        sd += fabsf(row[ca] - row[cl]) + fabsf(row[ca + 1] - row[cl + 1]) + fabsf(row[ca + 2] - row[cl + 2]);
       }
       sw = wave_sum(sw); sd = wave_sum(sd);
       if (lane == 0) { A.nreg.spv_ray[ray * 2] = sw; A.nreg.spv_ray[ray * 2 + 1] = sd; }
     }
     float var = 0.f;
     if (MODE == 1 || A.var) {
-#pragma unroll
-      for (int j = 0; j < BN_MAX_CPL; ++j) {
-        const int s = lane * cpl + j;
-        if (j < cpl && s < S) { const float dz = zv[j] - dsum; var += dz * dz * w[j]; }
-      }
+      BN_RAY_EACH(F, j, s) { const float dz = F.zv[j] - dsum; var += dz * dz * F.w[j]; }
       var = wave_sum(var);
       if (lane == 0 && A.var) A.var[ray] = var;
     }
@@ -983,114 +814,81 @@ template <int MODE, bool C4> __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) 
       dws -= dy * A.pad;
       if (lane == 0 && A.rgb) A.rgb[ray * 3 + c] = y;
     }
-    if (A.tdepth && A.valid[ray * A.v_stride] > 0.f) {
-      const float td = A.tdepth[ray * A.td_stride], tw = A.tweight[ray * A.tw_stride], ts = A.tstd[ray * A.ts_stride];
-      const bool apply = A.usealldepth || (fabsf(dsum - td) - ts > 0.f) || (ts < sqrtf(var));
-      if (apply) {
-        const float k = A.lambda_ds / 3.f / (float)A.R;
-        loss += k * tw * (dsum - td) * (dsum - td);
-        dd = k * 2.f * tw * (dsum - td);
-      }
-    }
-    // a ray whose loss term is not finite: with `nonfinite` (FusedTrainer.sanitize_grads) it is left out of the step - loss term 0,
-    // gradients 0 - and counted, as bn_ray_shade_loss does; without it the NaN reaches the loss and the gradients as upstream
-    if (A.nonfinite && !(fabsf(loss) <= 3.0e38f)) {
-      if (lane == 0) atomicAdd(A.nonfinite + (isnan(loss) ? 0 : 1), 1ull);
-      loss = 0.f; dd = 0.f; dws = 0.f;
+    depth_loss(A.prior, ray, dsum, var, A.lambda_ds, A.usealldepth, A.R, loss, dd);
+    // (without `nonfinite` the NaN reaches the loss and the gradients as upstream)
+    if (report_ray_loss(lane == 0, ray, loss, A.nonfinite, A.ray_loss, A.loss_acc, A.loss_slots)) {
+      dd = 0.f; dws = 0.f;
       dacc[0] = dacc[1] = dacc[2] = 0.f;
-    }
-    if (lane == 0) {
-      if (A.ray_loss) A.ray_loss[ray] = loss;
-      if (A.loss_acc) atomicAdd(A.loss_acc + (int)(ray % A.loss_slots), loss);
     }
   } else {
     dd = A.d_depth ? A.d_depth[ray] : 0.f;
     dws = A.d_wsum ? A.d_wsum[ray] : 0.f;
     for (int c = 0; c < C; ++c) dacc[c] = (A.d_acc && c != 3) ? A.d_acc[ray * C + c] : 0.f;
   }
-  // ---- backward: g_s = dL/dw_s; dL/dalpha_s = g_s T_s - (1/u_s) sum_{k>s} g_k w_k   
+  // ---- backward (RayFront::backward)
   const int ng = MODE == 1 ? 3 : C;
   const float hs = MODE == 2 ? A.hs_scale : 0.f, hs_depth = (MODE == 2 && A.hs_scale != 0.f) ? A.depth_in[ray] : 0.f;
-  const bool nreg_on = MODE == 2 && A.nreg.rays_d != nullptr;
-  float nvx = 0.f, nvy = 0.f, nvz = 0.f;
-  if (nreg_on) { const float *rd = A.nreg.rays_d + ray * A.nreg.rd_stride; nvx = -rd[0]; nvy = -rd[1]; nvz = -rd[2]; }
   const bool spv_on = MODE == 2 && A.nreg.lambda_spv != 0.f && A.nreg.spv_tot != nullptr;
   const float spv_w = spv_on ? A.nreg.spv_tot[0] : 0.f, spv_n = spv_on ? A.nreg.spv_tot[1] : 0.f;
-  float g[BN_MAX_CPL], gw = 0.f;
+  float g[BN_MAX_CPL] = {}, gw = 0.f;
+  BN_RAY_EACH(F, j, s) {
+    float gg = dd * F.zv[j] + dws;
+    if (MODE == 2 && A.d_weights) gg += A.d_weights[ray * S + s];
+    if (MODE == 2 && hs != 0.f) { const float dz = F.zv[j] - hs_depth; gg += hs * (dz * dz); }
+    if (MODE == 2 && spv_on) gg += spv_w;
+    if (nreg_on) {
 #pragma unroll
-  for (int j = 0; j < BN_MAX_CPL; ++j) {
-    g[j] = 0.f;
-    const int s = lane * cpl + j;
-    if (j < cpl && s < S) {
-      float gg = dd * zv[j] + dws;
-      if (MODE == 2 && A.d_weights) gg += A.d_weights[ray * S + s];
-      if (MODE == 2 && hs != 0.f) { const float dz = zv[j] - hs_depth; gg += hs * (dz * dz); }
-      if (MODE == 2 && spv_on) gg += spv_w;
-      if (MODE == 2 && nreg_on) {
+      for (int f = 0; f < 2; ++f) {
+        float lam, nv;
+        if (nreg_term(A.nreg, f, vx, vy, vz, [&](int c) { return chan(j, c); }, lam, nv)) gg += lam * nv * nv;
+      }
+    }
+    for (int c = 0; c < ng; ++c)
+      if (c != 3) gg += dacc[c] * chan(j, c);
+    g[j] = gg;
+    gw += gg * F.w[j];
+  }
+  unsigned int n_nan = 0, n_inf = 0;
+  F.backward(g, gw);      // g[j]: now d loss / d sigma_s
+  BN_RAY_EACH(F, j, s) {
+    const float wj = F.w[j];
+    float *drow = roff[j] >= 0 ? A.d_out1 + roff[j] : A.d_out2 + ~roff[j];
+    if (C4) {
+      f32x4 o = {wj * dacc[0], wj * dacc[1], wj * dacc[2], g[j]};
+      if (A.nonfinite) {
 #pragma unroll
-        for (int f = 0; f < 2; ++f) {
-          const int c0 = f == 0 ? A.nreg.ch_an : A.nreg.ch_lr;
-          const float lam = f == 0 ? A.nreg.lambda_an : A.nreg.lambda_lr;
-          if (c0 < 0 || !(lam > 0.f)) continue;
-          const float nv = fminf(chan(j, c0) * nvx + chan(j, c0 + 1) * nvy + chan(j, c0 + 2) * nvz, 0.f);
-          gg += lam * nv * nv;
+        for (int c = 0; c < 4; ++c) {
+          if (isnan(o[c])) { ++n_nan; o[c] = 0.f; }
+          else if (isinf(o[c])) { ++n_inf; o[c] = 0.f; }
         }
       }
-      for (int c = 0; c < ng; ++c)
-        if (c != 3) gg += dacc[c] * chan(j, c);
-      g[j] = gg;
-      gw += gg * w[j];
-    }
-  }
-  float suffix = wave_excl_sum_rev(gw, lane);
-  unsigned int n_nan = 0, n_inf = 0;
+      *(f32x4 *)drow = o;
+    } else {
+      float nr_g[2] = {0.f, 0.f};        // 2 lambda w_s min(0, n_s . view): times view[c - c0] on the normal's channels
+      if (nreg_on) {
 #pragma unroll
-  for (int j = BN_MAX_CPL - 1; j >= 0; --j) {
-    const int s = lane * cpl + j;
-    if (j < cpl && s < S) {
-      const float dalpha = g[j] * tr[j] - suffix / u[j];
-      suffix += g[j] * w[j];
-      float *drow = roff[j] >= 0 ? A.d_out1 + roff[j] : A.d_out2 + ~roff[j];
-      if (C4) {
-        f32x4 o = {w[j] * dacc[0], w[j] * dacc[1], w[j] * dacc[2], dalpha * dad[j]};
-        if (A.nonfinite) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            if (isnan(o[c])) { ++n_nan; o[c] = 0.f; }
-            else if (isinf(o[c])) { ++n_inf; o[c] = 0.f; }
-          }
+        for (int f = 0; f < 2; ++f) {
+          float lam, nv;
+          if (nreg_term(A.nreg, f, vx, vy, vz, [&](int c) { return chan(j, c); }, lam, nv)) nr_g[f] = 2.f * lam * wj * nv;
         }
-        *(f32x4 *)drow = o;
-      } else {
-        float nr_g[2] = {0.f, 0.f};        // 2 lambda w_s min(0, n_s . view): times view[c - c0] on the normal's channels
+      }
+      for (int c = 0; c < C; ++c) {
+        float v = c == 3 ? g[j] : (c < ng ? wj * dacc[c] : 0.f);
         if (nreg_on) {
-#pragma unroll
-          for (int f = 0; f < 2; ++f) {
-            const int c0 = f == 0 ? A.nreg.ch_an : A.nreg.ch_lr;
-            const float lam = f == 0 ? A.nreg.lambda_an : A.nreg.lambda_lr;
-            if (c0 < 0 || !(lam > 0.f)) continue;
-            const float nv = fminf(chan(j, c0) * nvx + chan(j, c0 + 1) * nvy + chan(j, c0 + 2) * nvz, 0.f);
-            nr_g[f] = 2.f * lam * w[j] * nv;
-          }
+          const int ca = c - A.nreg.ch_an, cl = c - A.nreg.ch_lr;
+          if (A.nreg.ch_an >= 0 && ca >= 0 && ca < 3) v += nr_g[0] * (ca == 0 ? vx : ca == 1 ? vy : vz);
+          if (A.nreg.ch_lr >= 0 && cl >= 0 && cl < 3) v += nr_g[1] * (cl == 0 ? vx : cl == 1 ? vy : vz);
         }
-        for (int c = 0; c < C; ++c) {
-          float v = c == 3 ? dalpha * dad[j] : (c < ng ? w[j] * dacc[c] : 0.f);
-          if (nreg_on) {
-            const int ca = c - A.nreg.ch_an, cl = c - A.nreg.ch_lr;
-            if (A.nreg.ch_an >= 0 && ca >= 0 && ca < 3) v += nr_g[0] * (ca == 0 ? nvx : ca == 1 ? nvy : nvz);
-            if (A.nreg.ch_lr >= 0 && cl >= 0 && cl < 3) v += nr_g[1] * (cl == 0 ? nvx : cl == 1 ? nvy : nvz);
-          }
-          if (spv_on) {     // d |n_an - n_lr| / d n: the sign of the difference (0 at 0, as torch's L1), opposite on the two fields
-            const int ka = c - A.nreg.spv_ch_an, kl = c - A.nreg.spv_ch_lr;
-            if (ka >= 0 && ka < 3) { const float d = chan(j, c) - chan(j, A.nreg.spv_ch_lr + ka); v += spv_n * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)); }
-            if (kl >= 0 && kl < 3) { const float d = chan(j, A.nreg.spv_ch_an + kl) - chan(j, c); v -= spv_n * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)); }
-          }
-          if (A.nonfinite) {
-            if (isnan(v)) { ++n_nan; v = 0.f; }
-            else if (isinf(v)) { ++n_inf; v = 0.f; }
-          }
-          drow[c] = v;
+        if (spv_on) {     // d |n_an - n_lr| / d n: the sign of the difference (0 at 0, as torch's L1), opposite on the two fields
+          const int ka = c - A.nreg.spv_ch_an, kl = c - A.nreg.spv_ch_lr;
+          if (ka >= 0 && ka < 3) { const float d = chan(j, c) - chan(j, A.nreg.spv_ch_lr + ka); v += spv_n * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)); }
+          if (kl >= 0 && kl < 3) { const float d = chan(j, A.nreg.spv_ch_an + kl) - chan(j, c); v -= spv_n * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)); }
         }
+        if (A.nonfinite) {
+          if (isnan(v)) { ++n_nan; v = 0.f; }
+          else if (isinf(v)) { ++n_inf; v = 0.f; }
+        }
+        drow[c] = v;
       }
     }
   }
@@ -1134,10 +932,27 @@ extern "C" int bn_normal_spv_reduce(const float *spv_ray, int64_t R, int32_t S, 
   return 0;
 }
 
-static int merged_check(const MergedArgs &a, const char *what) {
+// The fields every merged entry point fills, and the clauses it puts to them (`what`: the entry's name, the head of the message)
+static int merged_args(MergedArgs &a, const char *what, const float *z, const int64_t *sort_idx, const float *out1, const float *out2,
+                       int32_t S1, int32_t S2, int32_t C, int64_t R, const bn_noise *noise) {
+  a = MergedArgs{};
+  a.noise = make_noise(noise);
+  a.z = z; a.idx = sort_idx; a.out1 = out1; a.out2 = out2; a.S1 = S1; a.S2 = S2; a.C = C; a.R = R;
   BN_REQUIRE(a.z && a.out1 && a.R > 0 && a.S2 >= 1 && a.S2 <= 64 * BN_MAX_CPL && a.S1 >= 1 && a.S1 <= a.S2, "%s: bad arguments (S1=%d S2=%d)", what, a.S1, a.S2);
   BN_REQUIRE(a.C >= 4 && a.C <= BN_MAX_CH, "%s: C=%d unsupported", what, a.C);
   BN_REQUIRE(a.S1 == a.S2 || (a.idx && a.out2), "%s: a merged set needs sort_idx and the second block", what);
+  return 0;
+}
+// The regulariser / NormalLoss channels of a bn_normal_reg.  spv: the NormalLoss buffer this direction uses (forward spv_ray,
+// backward spv_tot); reg_ok: the forward has somewhere to write the regulariser term
+static int merged_nreg_check(const bn_normal_reg *nreg, int C, const float *spv, bool reg_ok, const char *what) {
+  auto in_row = [&](int ch) { return ch >= 4 && ch + 3 <= C; };
+  if (nreg && nreg->lambda_spv != 0.f)
+    BN_REQUIRE(spv && in_row(nreg->spv_ch_an) && in_row(nreg->spv_ch_lr), "%s: bad NormalLoss arguments (channels %d, %d)", what,
+               nreg->spv_ch_an, nreg->spv_ch_lr);
+  if (nreg && nreg->rays_d)
+    BN_REQUIRE(reg_ok && (nreg->ch_an < 0 || in_row(nreg->ch_an)) && (nreg->ch_lr < 0 || in_row(nreg->ch_lr)),
+               "%s: bad normal-regulariser channels (%d, %d)", what, nreg->ch_an, nreg->ch_lr);
   return 0;
 }
 #define MERGED_GRID(R) dim3((unsigned)ceil_div64(R, WAVES_PER_BLOCK)), 64 * WAVES_PER_BLOCK, 0, (hipStream_t)stream
@@ -1149,18 +964,11 @@ extern "C" int bn_merged_composite_forward(const float *z, const int64_t *sort_i
                                            int32_t S2, int32_t C, int64_t R, float *alphas, float *trans, float *weights, float *depth,
                                            float *acc, float *wsum, float *var, const bn_normal_reg *nreg, float *reg_out,
                                            const bn_noise *noise, void *stream) {
-  MergedArgs a = {};
-  a.noise = make_noise(noise);
-  a.z = z; a.idx = sort_idx; a.out1 = out1; a.out2 = out2; a.S1 = S1; a.S2 = S2; a.C = C; a.R = R;
+  MergedArgs a;
+  if (int e = merged_nreg_check(nreg, C, nreg ? nreg->spv_ray : nullptr, reg_out != nullptr, "merged_composite_forward")) return e;
+  if (int e = merged_args(a, "merged_composite_forward", z, sort_idx, out1, out2, S1, S2, C, R, noise)) return e;
   a.alphas = alphas; a.trans = trans; a.weights = weights; a.depth = depth; a.acc = acc; a.wsum = wsum; a.var = var;
-  if (nreg && nreg->lambda_spv != 0.f)
-    BN_REQUIRE(nreg->spv_ray && nreg->spv_ch_an >= 4 && nreg->spv_ch_an + 3 <= C && nreg->spv_ch_lr >= 4 && nreg->spv_ch_lr + 3 <= C,
-               "merged_composite_forward: bad NormalLoss arguments (channels %d, %d)", nreg->spv_ch_an, nreg->spv_ch_lr);
-  if (nreg && nreg->rays_d)
-    BN_REQUIRE(reg_out && (nreg->ch_an < 0 || (nreg->ch_an >= 4 && nreg->ch_an + 3 <= C)) && (nreg->ch_lr < 0 || (nreg->ch_lr >= 4 && nreg->ch_lr + 3 <= C)),
-               "merged_composite_forward: bad normal-regulariser channels (%d, %d)", nreg->ch_an, nreg->ch_lr);
   if (nreg && (nreg->rays_d || nreg->lambda_spv != 0.f)) { a.nreg = *nreg; a.reg_out = reg_out; }
-  if (int e = merged_check(a, "merged_composite_forward")) return e;
   BnProfScope prof_(BN_K_COMPOSITE_FWD, (hipStream_t)stream);
   if (merged_c4(a)) merged_composite_kernel<0, true><<<MERGED_GRID(R)>>>(a);
   else merged_composite_kernel<0, false><<<MERGED_GRID(R)>>>(a);
@@ -1173,19 +981,12 @@ extern "C" int bn_merged_composite_backward(const float *z, const int64_t *sort_
                                             const float *d_acc, const float *d_wsum, float hs_scale, const float *depth,
                                             const bn_normal_reg *nreg, float *d_out1, float *d_out2, unsigned long long *nonfinite,
                                             const bn_noise *noise, void *stream) {
-  MergedArgs a = {};
-  a.noise = make_noise(noise);
-  a.z = z; a.idx = sort_idx; a.out1 = out1; a.out2 = out2; a.S1 = S1; a.S2 = S2; a.C = C; a.R = R;
+  MergedArgs a;
+  if (int e = merged_nreg_check(nreg, C, nreg ? nreg->spv_tot : nullptr, true, "merged_composite_backward")) return e;
+  if (int e = merged_args(a, "merged_composite_backward", z, sort_idx, out1, out2, S1, S2, C, R, noise)) return e;
   a.d_weights = d_weights; a.d_depth = d_depth; a.d_acc = d_acc; a.d_wsum = d_wsum; a.d_out1 = d_out1; a.d_out2 = d_out2;
   a.nonfinite = nonfinite; a.hs_scale = hs_scale; a.depth_in = depth;
-  if (nreg && nreg->lambda_spv != 0.f)
-    BN_REQUIRE(nreg->spv_tot && nreg->spv_ch_an >= 4 && nreg->spv_ch_an + 3 <= C && nreg->spv_ch_lr >= 4 && nreg->spv_ch_lr + 3 <= C,
-               "merged_composite_backward: bad NormalLoss arguments (channels %d, %d)", nreg->spv_ch_an, nreg->spv_ch_lr);
-  if (nreg && nreg->rays_d)
-    BN_REQUIRE((nreg->ch_an < 0 || (nreg->ch_an >= 4 && nreg->ch_an + 3 <= C)) && (nreg->ch_lr < 0 || (nreg->ch_lr >= 4 && nreg->ch_lr + 3 <= C)),
-               "merged_composite_backward: bad normal-regulariser channels (%d, %d)", nreg->ch_an, nreg->ch_lr);
   if (nreg && (nreg->rays_d || nreg->lambda_spv != 0.f)) a.nreg = *nreg;
-  if (int e = merged_check(a, "merged_composite_backward")) return e;
   BN_REQUIRE(hs_scale == 0.f || depth, "merged_composite_backward: hs_scale needs the forward's depth");
   BN_REQUIRE(d_out1 && (S1 == S2 || d_out2), "merged_composite_backward: null gradient buffer");
   BnProfScope prof_(BN_K_COMPOSITE_BWD, (hipStream_t)stream);
@@ -1202,17 +1003,14 @@ extern "C" int bn_lambert_tail(const float *z, const int64_t *sort_idx, const fl
                                int32_t usealldepth, float *ray_loss, float *loss_acc, int32_t loss_slots, float *rgb,
                                float *weights, float *depth, float *d_out1, float *d_out2, unsigned long long *nonfinite,
                                const bn_noise *noise, void *stream) {
-  MergedArgs a = {};
-  a.noise = make_noise(noise);
-  a.z = z; a.idx = sort_idx; a.out1 = out1; a.out2 = out2; a.S1 = S1; a.S2 = S2; a.C = C; a.R = R;
-  a.rgbs = rgbs; a.valid = valid_depth; a.tdepth = target_depth; a.tweight = target_weight; a.tstd = target_std;
-  a.v_stride = v_stride; a.td_stride = td_stride; a.tw_stride = tw_stride; a.ts_stride = ts_stride;
+  MergedArgs a;
+  if (int e = merged_args(a, "lambert_tail", z, sort_idx, out1, out2, S1, S2, C, R, noise)) return e;
+  a.rgbs = rgbs; a.prior = DepthPrior{valid_depth, target_depth, target_weight, target_std, v_stride, td_stride, tw_stride, ts_stride};
   a.pad = rgb_padding; a.lambda_rgb = lambda_rgb; a.lambda_ds = lambda_ds; a.usealldepth = usealldepth;
   a.ray_loss = ray_loss; a.loss_acc = loss_acc; a.loss_slots = loss_slots > 0 ? loss_slots : 1; a.rgb = rgb; a.weights = weights; a.depth = depth; a.d_out1 = d_out1; a.d_out2 = d_out2;
   a.nonfinite = nonfinite;
-  if (int e = merged_check(a, "lambert_tail")) return e;
   BN_REQUIRE(rgbs && d_out1 && (S1 == S2 || d_out2), "lambert_tail: null argument");
-  BN_REQUIRE(!target_depth || (valid_depth && target_weight && target_std), "lambert_tail: incomplete depth prior");
+  if (int e = depth_prior_check(a.prior, true, "lambert_tail")) return e;
   BnProfScope prof_(BN_K_COMPOSITE_BWD, (hipStream_t)stream);
   if (merged_c4(a)) merged_composite_kernel<1, true><<<MERGED_GRID(R)>>>(a);
   else merged_composite_kernel<1, false><<<MERGED_GRID(R)>>>(a);

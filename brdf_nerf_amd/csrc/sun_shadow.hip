@@ -25,6 +25,7 @@
 #pragma clang fp contract(off)
 #include "brdf_eval.h"
 #include "shade_row.h"
+#include "composite_ray.h"
 
 namespace {
 
@@ -80,13 +81,9 @@ struct SunShadeArgs {
 // directions a block of the per-sample mode walks together: a sample's row is read and unpacked once for all of them
 constexpr int SUN_KT = 4;
 
-// alpha of one sample as bn_composite_forward forms it (render_kernels.hip composite_kernel) -> 1 - alpha + 1e-10
+// 1 - alpha + 1e-10 of one sample: the alpha step of the compositing kernels (composite_ray.h)
 __device__ __forceinline__ float sun_step(const float *zr, const float *sr, int t, bool last) {
-  const float delta = last ? 1e10f : zr[t + 1] - zr[t];
-  const float sg = sr[t];
-  const float rs = sg > 0.f ? sg : 0.f;
-  const float al = 1.f - expf(-delta * rs);
-  return 1.f - al + 1e-10f;
+  return alpha_step(last ? 1e10f : zr[t + 1] - zr[t], sr[t]).u;
 }
 
 // KIND / MASK: shade_row.h.  SAMPLES false: one BRDF per ray from the composited sums, rgb = clamp(T_{G-1} BRDF); true: the
