@@ -27,6 +27,31 @@ def allreduce_sum_(flat_grad, group=None):
     return flat_grad
 
 
+def allreduce_(t, op=None, group=None):
+    """In-place all-reduce (op None: SUM) of a small result tensor (integer sums, counters): gloo reduces host tensors, so under
+    it the tensor goes through the host; nccl (RCCL) reduces in place on the device.  Returns t; on one rank, t as it came."""
+    if world_info(group)[1] > 1:
+        op = dist.ReduceOp.SUM if op is None else op
+        if dist.get_backend(group) == "gloo":
+            h = t.cpu()
+            dist.all_reduce(h, op=op, group=group)
+            t.copy_(h)
+        else:
+            dist.all_reduce(t, op=op, group=group)
+    return t
+
+
+def row_band(what, H, rows=None, group=None):
+    """The rows [row0, row1) of an H-row grid this process works on: `rows` as given, else this rank's shard_bounds (all H rows
+    on one rank).  `what` names the caller in the ValueError of a band outside [0, H]."""
+    if rows is None:
+        rows = shard_bounds(H, *world_info(group))
+    rows = (int(rows[0]), int(rows[1]))
+    if not 0 <= rows[0] <= rows[1] <= H:
+        raise ValueError(f"{what}: rows {rows} outside [0, {H}]")
+    return rows
+
+
 def gather_rows(local, group=None):
     """Eval: all-gather per-ray results (R/W, C) -> (R, C) (rows in rank order)."""
     _, world = world_info(group)

@@ -9,7 +9,7 @@ through rasterio / gdal compute the MAE (sat_utils.py:185-350).  Here:
   Grid             the raster: from_cloud (the bounds rule of :665-671) or from_roi (the ground truth's grid, :658-663)
   point_cloud      (east, north, altitude) of every ray in float64 (:613-633); altitude_image its third column (eval.py:170-172)
   DsmAccumulator   bn_dsm_splat into an int64 (sum, count) grid - chunk by chunk, view by view, rank by rank - and bn_dsm_resolve
-  dsm_image        evaluate.render_image's loop with each chunk's depth splatted as it is produced (fill=True: and the holes
+  dsm_image        render_image's walk (viewwalk.py) with each chunk's depth splatted as it is produced (fill=True: and the holes
                    filled, fill.fill_holes)
   altitude_mae     the z-registered mean absolute altitude error (sat_utils.py:235, 246, 340-349)
 
@@ -143,16 +143,9 @@ class DsmAccumulator:
         return self
 
     def merge(self, group=None):
-        import torch.distributed as dist
-        from .distributed import world_info
-        if world_info(group)[1] > 1:
-            for t in (self.acc, self._skipped):
-                if dist.get_backend(group) == "gloo":          # gloo reduces host tensors; nccl (RCCL) reduces in place on the device
-                    h = t.cpu()
-                    dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
-                    t.copy_(h)
-                else:
-                    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        from .distributed import allreduce_
+        for t in (self.acc, self._skipped):
+            allreduce_(t, group=group)
         return self
 
     @property
@@ -177,24 +170,20 @@ def dsm_image(models, args, rays, frame, grid=None, chunk=None, group=None, radi
     replaced by its nearest known cell (fill.fill_holes; with a group each rank fills a band of rows).
     -> {"dsm" (H, W) float32, "count" (H, W) int32, "depth" (R,), "altitude" (R,) float64, "grid", "skipped"}
     (+ "dsm_grid" (H, W) float32 without NaN, "holes", "max_dist" with fill)"""
-    from .distributed import gather_rows, shard_bounds, world_info
     from .rendering import render_rays
-    rank, world = world_info(group)
-    lo, hi = shard_bounds(rays.shape[0], rank, world)
-    mine = rays[lo:hi]
-    chunk = chunk or args.chunk
+    from .viewwalk import ViewWalk
+    walk = ViewWalk(rays.shape[0], chunk or args.chunk, group)
     acc = None if grid is None else DsmAccumulator(grid, rays.device, radius, footprint)
     parts = []
-    for i in range(0, mine.shape[0], chunk):
-        out, _ = render_rays(models, args, mine[i:i + chunk], None, mode="test", **render_kw)
+    for i, j in walk.chunks():
+        out, _ = render_rays(models, args, rays[i:j], None, mode="test", **render_kw)
         parts.append(out["depth_coarse"])
         if acc is not None:
-            acc.add(mine[i:i + chunk], parts[-1], frame)
-    local = torch.cat(parts, 0) if parts else rays.new_zeros((0,))
-    depth = gather_rows(local, group) if world > 1 else local
+            acc.add(rays[i:j], parts[-1], frame)
+    depth = walk.join(parts, (), rays.dtype, rays.device)
     if acc is None:
         grid = _cloud_grid(rays, depth, frame, resolution)
-        acc = DsmAccumulator(grid, rays.device, radius, footprint).add(mine, local, frame)
+        acc = DsmAccumulator(grid, rays.device, radius, footprint).add(rays[walk.lo:walk.hi], depth[walk.lo:walk.hi], frame)
     acc.merge(group)
     dsm, count = acc.result()
     res = {"dsm": dsm, "count": count, "depth": depth, "altitude": altitude_image(rays, depth, frame), "grid": grid,

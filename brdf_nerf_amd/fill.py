@@ -30,17 +30,6 @@ import torch
 from . import functions as Fn
 
 
-def _allreduce(t, op, group):
-    import torch.distributed as dist
-    if dist.get_backend(group) == "gloo":          # gloo reduces host tensors; nccl (RCCL) reduces in place on the device
-        h = t.cpu()
-        dist.all_reduce(h, op=op, group=group)
-        t.copy_(h)
-    else:
-        dist.all_reduce(t, op=op, group=group)
-    return t
-
-
 @torch.no_grad()
 def fill_holes(dsm, rows=None, group=None, want_source=False):
     """quickly_interpolate_nans_from_singlechannel_img(dsm) on the device.  dsm: (H, W) float32, contiguous, NaN = hole.
@@ -50,15 +39,11 @@ def fill_holes(dsm, rows=None, group=None, want_source=False):
     with `rows`, the rows outside the band are returned as they came (holes included) and `source` is -1 there.
     -> {"filled" (H, W) float32, "holes" int, "max_dist" float = sqrt(largest d2)} (+ "source" (H, W) int32 flat indices)."""
     import torch.distributed as dist
-    from .distributed import gather_rows, shard_bounds, world_info
+    from .distributed import allreduce_, gather_rows, row_band, world_info
     Fn._fill_grid("fill_holes", dsm, torch.float32, "dsm")
     H, W = dsm.shape
-    rank, world = world_info(group)
-    if rows is None:
-        rows = shard_bounds(H, rank, world) if world > 1 else (0, H)
-    rows = (int(rows[0]), int(rows[1]))
-    if not 0 <= rows[0] <= rows[1] <= H:
-        raise ValueError(f"fill_holes: rows {rows} outside [0, {H}]")
+    _, world = world_info(group)
+    rows = row_band("fill_holes", H, rows, group)
     near_row = Fn.grid_nearest_col(dsm)                    # refuses a host tensor before any launch
     if int(near_row.max()) < 0:
         raise ValueError(f"fill_holes: the {H} x {W} grid has no known cell (every cell is NaN)")
@@ -70,8 +55,8 @@ def fill_holes(dsm, rows=None, group=None, want_source=False):
         if dst.shape[0] != H:
             raise ValueError(f"fill_holes: the ranks' bands cover {dst.shape[0]} rows of {H}")
         holes, far = counts[0:1].clone(), counts[1:2].clone()
-        _allreduce(holes, dist.ReduceOp.SUM, group)
-        _allreduce(far, dist.ReduceOp.MAX, group)
+        allreduce_(holes, dist.ReduceOp.SUM, group)
+        allreduce_(far, dist.ReduceOp.MAX, group)
         counts = torch.cat([holes, far])
     elif rows != (0, H):
         band = torch.zeros((H, 1), dtype=torch.bool, device=dsm.device)

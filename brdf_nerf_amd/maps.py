@@ -10,7 +10,7 @@ device and only ray-level results are kept:
                  integer counts of NormalRegLoss's perc_ng_nr and check_vec0
   point_normals  bn_point_normals: sat_utils.calc_normal_from_pts3d (:16-50) on an (H, W, 3) image of points
   depth_normals  calc_normal_from_depth_v2 (datasets/satellite_rgb_dep.py:578-584): point_cloud + point_normals
-  view_maps      render_image's loop with the reductions in it: the maps, the logged scalars and (cross_rows=) the per-sample
+  view_maps      render_image's walk (viewwalk.py) with the reductions in it: the maps, the logged scalars and (cross_rows=) the per-sample
                  values of one image row, the dump of main.py:567-595
 
 precision: 'reference' rounds the UTM points to float32 before differencing them, as upstream's `.type(torch.FloatTensor)`
@@ -134,17 +134,16 @@ def view_maps(models, args, rays, H, W, frame=None, chunk=None, apply_brdf=False
       row h only, sliced out of the chunks that hold it; writing the text file is the caller's business.
     Under a `group` every rank reduces its share, the rows are gathered and the counters merge by one SUM all-reduce.
     Refused: gsam_only=True and --sun_v analystic (NotImplementedError), visu_scale != 1, H W != rays.shape[0]."""
-    from .distributed import gather_rows, shard_bounds, world_info
+    from .distributed import allreduce_
     from .dsm import altitude_image
-    from .rendering import _composite_merged, _sample_passes, shade
+    from .rendering import _merged_geometry, shade
+    from .viewwalk import ViewWalk
     model = models["coarse"]
     if gsam_only:
         raise NotImplementedError("view_maps does not cover gsam_only=True: the maps are reduced from the merged S + G sample set of "
                                   "the default evaluation path")
     round_f32 = _check(model, args, rays, H, W, precision, cross_rows)
-    rank, world = world_info(group)
-    lo, hi = shard_bounds(rays.shape[0], rank, world)
-    chunk = chunk or args.chunk
+    walk = ViewWalk(rays.shape[0], chunk or args.chunk, group)
     dev = rays.device
     counters = torch.zeros((2, len(RAY_MAP_COUNTERS)), dtype=torch.int64, device=dev)       # rows: normal_an | normal_lr
     parts, cross, brdf_type, main_row = {}, {k: [] for k in CROSS_KEYS}, "Lambertian", 0
@@ -153,11 +152,9 @@ def view_maps(models, args, rays, H, W, frame=None, chunk=None, apply_brdf=False
     def keep(key, t):
         parts.setdefault(key, []).append(t)
 
-    for i in range(lo, hi, chunk):
-        j = min(hi, i + chunk)
-        # render_rays' body (rendering.py), kept in step with it: the same calls in the same order draw the same numbers
-        p = _sample_passes(models, args, rays[i:j], None, "test", None, None, None, apply_brdf, False, False, False, apply_theta)
-        out, alphas, transparency, weights, depth, acc = _composite_merged(p, args)
+    for i, j in walk.chunks():
+        p, (out, alphas, transparency, weights, depth, acc) = _merged_geometry(models, args, rays[i:j], apply_brdf=apply_brdf,
+                                                                               apply_theta=apply_theta)
         res, brdf_type = shade(model, args, p.spec, out, p.z_all, alphas, transparency, weights, depth, acc, p.rays_d, p.sun_d,
                                apply_brdf, cos_irra_on, p.idx, None)
         spec, R = p.spec, j - i
@@ -206,22 +203,13 @@ def view_maps(models, args, rays, H, W, frame=None, chunk=None, apply_brdf=False
                            ("sort_idx", p.idx), ("depth", depth), ("std", std)):
                 cross[key].append(t[a:max(a, b)].clone())
 
-    if not parts:                       # a rank without rays still takes part in the gathers below
-        raise ValueError(f"view_maps: rank {rank} of {world} has no ray of a view of {rays.shape[0]} rays")
-    maps = {}
-    for key, v in parts.items():
-        t = torch.cat(v, 0).contiguous()
-        maps[key] = gather_rows(t, group) if world > 1 else t
+    if not parts:                       # the maps a rank keeps depend on the chunks it rendered: without one it cannot name them
+        raise ValueError(f"view_maps: rank {walk.rank} of {walk.world} has no ray of a view of {rays.shape[0]} rays")
+    maps = {key: walk.join(v, v[0].shape[1:]) for key, v in parts.items()}
     result = {"maps": maps, "brdf_type": brdf_type}
     if cross_rows is not None:
-        result["cross"] = {}
-        for key, v in cross.items():
-            t = torch.cat(v, 0)
-            result["cross"][key] = gather_rows(t, group) if world > 1 else t
-    if world > 1:
-        from .metrics import _allreduce_sum
-        _allreduce_sum(counters, group)
-    host = counters.cpu()
+        result["cross"] = {key: walk.join(v, v[0].shape[1:]) for key, v in cross.items()}
+    host = allreduce_(counters, group=group).cpu()
     c = host[main_row]
     n_an = int(host[0, 5]) if main_row == 0 else 0
     n_lr = int(host[1, 5])

@@ -186,17 +186,6 @@ def normal_angle_mae(dsm, gt, resolution, mask=None, border="reference"):
             "mae_nr_out": _angle_value(s[4], s[5]) if mask is not None else -1}
 
 
-def _allreduce_sum(t, group):
-    import torch.distributed as dist
-    if dist.get_backend(group) == "gloo":          # gloo reduces host tensors; nccl (RCCL) reduces in place on the device
-        h = t.cpu()
-        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
-        t.copy_(h)
-    else:
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-    return t
-
-
 @torch.no_grad()
 def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=None, grid=None, dsm_mask=None, group=None,
                window=3, layout="reference", radius=1, footprint="disc", resolution=0.5, register="z", **render_kw):
@@ -213,9 +202,10 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
     from the normals of the REGISTERED DSM, and also "dx", "dy", "rdsm".
     -> {"psnr", "psnr_scl", "ssim", "ssim_scl", "ssim_skipped", "ssim_sums", "rgb", "depth"} (+ "dsm", "count", "grid",
     "skipped" with a frame; + "mae", "mae_in", "mae_out", "mae_nr", "mae_nr_in", "mae_nr_out", "shift" with gt_dsm)."""
-    from .distributed import shard_bounds, world_info
+    from .distributed import allreduce_, row_band
     from .dsm import DsmAccumulator, _cloud_grid, altitude_mae
     from .evaluate import render_image
+    from .viewwalk import ViewWalk
     if rays.shape[0] != H * W:
         raise ValueError(f"score_view: {rays.shape[0]} rays for a view of {H} x {W}")
     if register not in ("z", "xy"):
@@ -223,24 +213,20 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
     if gt_dsm is not None and frame is None:
         raise ValueError("score_view: gt_dsm needs the scene's frame (frame=) to build the DSM it is compared with")
     check_window(window, H, W)
-    rank, world = world_info(group)
     view = render_image(models, args, rays, None, keys=("rgb", "depth"), group=group, **render_kw)
     rgb, depth = view["rgb"], view["depth"]
     rgbs = rgbs.to(rgb.device)
     res = {"rgb": rgb, "depth": depth}
     p, p_scl = image_psnr(rgb, rgbs, mask=mask, scl=True)
     res["psnr"], res["psnr_scl"] = float(p), float(p_scl)
-    band = shard_bounds(H, rank, world)
-    sums, _, _ = _ssim_sums(rgb, rgbs, H, W, mask, window, layout, True, band, False)
-    if world > 1:
-        _allreduce_sum(sums, group)
-    host = sums.cpu()
+    sums, _, _ = _ssim_sums(rgb, rgbs, H, W, mask, window, layout, True, row_band("score_view", H, None, group), False)
+    host = allreduce_(sums, group=group).cpu()
     res.update(ssim=_ssim_value(host[0]), ssim_scl=_ssim_value(host[1]), ssim_skipped=int(host[0, 2]), ssim_sums=host)
     if frame is not None:
-        lo, hi = shard_bounds(rays.shape[0], rank, world)
+        walk = ViewWalk(rays.shape[0], render_kw.get("chunk") or args.chunk, group)     # render_image's: the rays this rank rendered
         if grid is None:
             grid = _cloud_grid(rays, depth, frame, resolution)
-        acc = DsmAccumulator(grid, rays.device, radius, footprint).add(rays[lo:hi], depth[lo:hi], frame).merge(group)
+        acc = DsmAccumulator(grid, rays.device, radius, footprint).add(rays[walk.lo:walk.hi], depth[walk.lo:walk.hi], frame).merge(group)
         dsm, count = acc.result()
         res.update(dsm=dsm, count=count, grid=grid, skipped=acc.skipped)
         if gt_dsm is not None:

@@ -99,20 +99,14 @@ def register_xy(dsm, gt, irange=5, min_size=100, rows=None, group=None):
     of the moments per level merges them: every rank returns the single-process result, bit for bit.
     -> {"dx", "dy", "b", "k", "pivot", "levels": [(H, W, dx, dy), ...] coarsest first, "moments": [(2 irange + 1)^2 x 6 int64
     host tensor per level], "skipped"}."""
-    from .distributed import shard_bounds, world_info
-    from .metrics import _allreduce_sum
+    from .distributed import allreduce_, row_band
     v, u = _grid_pair("register_xy", dsm, gt)
     if not isinstance(irange, int) or not 0 <= irange <= L.BN_NCC_MAX_RANGE:
         raise ValueError(f"register_xy: irange {irange!r} outside [0, {L.BN_NCC_MAX_RANGE}]")
     if not v.is_cuda:
         raise ValueError("register_xy: the grids must be on the device (there is no host path)")
     H, W = u.shape
-    rank, world = world_info(group)
-    if rows is None:
-        rows = shard_bounds(H, rank, world) if world > 1 else (0, H)
-    rows = (int(rows[0]), int(rows[1]))
-    if not 0 <= rows[0] <= rows[1] <= H:
-        raise ValueError(f"register_xy: rows {rows} outside [0, {H}]")
+    rows = row_band("register_xy", H, rows, group)
     u, v = u.double().contiguous(), v.double().contiguous()
     inf = torch.full((), math.inf, dtype=torch.float64, device=u.device)
     both = torch.stack([u, v])
@@ -131,14 +125,11 @@ def register_xy(dsm, gt, irange=5, min_size=100, rows=None, group=None):
         lu, lv = pyramid[level]
         dx0, dy0 = 2 * dx, 2 * dy                           # (0, 0) at the coarsest level: upstream's 0 // 2 all the way down
         sums, _ = Fn.ncc_moments(lu, lv, pivot, k, dx0, dy0, irange, skipped=skipped, rows=_band(rows, level))
-        if world > 1:
-            _allreduce_sum(sums, group)
-        host = sums.cpu()
+        host = allreduce_(sums, group=group).cpu()
         dx, dy, at = best_shift(host.tolist(), dx0, dy0, irange)
         levels.append((lu.shape[0], lu.shape[1], dx, dy))
         moments.append(host)
-    if world > 1:
-        _allreduce_sum(skipped, group)
+    allreduce_(skipped, group=group)
     if at is None:                                          # no shift of level 0 can win: the offset of the start, if it has a pair
         at = ((2 * irange + 1) ** 2) // 2
     N, Su, Sv = (int(x) for x in moments[-1][at][:3])

@@ -23,7 +23,8 @@ itself depends on the sun through a field pass: shadows.py serves that model), g
 import torch
 
 from . import functions as Fn
-from .rendering import _composite_merged, _sample_passes, shade_desc
+from .rendering import _field_spec, _merged_geometry, shade_desc
+from .viewwalk import ViewWalk, check_out
 
 # directions of one bn_ray_shade_dirs launch at most: bounds the (K, R, 3) result a launch writes when `out` lives on the host
 _TILE_BYTES = 1 << 30
@@ -80,6 +81,12 @@ class Surface:
     def n_rays(self):
         return self.acc.shape[0]
 
+    @staticmethod
+    def row_table(spec, args, per_sample):
+        """(attribute, trailing shape) of the per-ray tensors that ViewWalk.join_attrs joins."""
+        C, SG = spec.out_channels, args.n_samples + args.guided_samples
+        return [("acc", (C,)), ("wsum", ()), ("depth", ())] + ([("rows", (SG, C)), ("weights", (SG,))] if per_sample else [])
+
     def select(self, rows):
         """The surface of the chosen rays (rows: indices, a slice or a mask)."""
         if not isinstance(rows, slice):
@@ -110,45 +117,26 @@ def render_surface(models, args, rays, ts=None, chunk=None, apply_brdf=False, ap
     chunk by chunk instead of holding them.
     -> Surface."""
     _check_relightable(models["coarse"], args, gsam_only, per_sample)
-    parts = [c for _, _, c in _surface_chunks(models, args, rays, ts, chunk, apply_brdf, apply_theta, group, bTestNormal, per_sample)]
-    return _join_surfaces(parts, models, args, rays, apply_brdf, apply_theta, bTestNormal, per_sample, group)
+    walk = ViewWalk(rays.shape[0], chunk or args.chunk, group)
+    parts = [c for _, _, c in _surface_chunks(walk, models, args, rays, ts, apply_brdf, apply_theta, bTestNormal, per_sample)]
+    return _join_surfaces(walk, parts, models, args, rays, apply_brdf, apply_theta, bTestNormal, per_sample)
 
 
-def _surface_chunks(models, args, rays, ts, chunk, apply_brdf, apply_theta, group, bTestNormal, per_sample):
+def _surface_chunks(walk, models, args, rays, ts, apply_brdf, apply_theta, bTestNormal, per_sample):
     """The geometry of this rank's share of the rays, chunk by chunk: yields (i, j, Surface of rays[i:j])."""
-    from .distributed import shard_bounds, world_info
-    rank, world = world_info(group)
-    lo, hi = shard_bounds(rays.shape[0], rank, world)
-    chunk = chunk or args.chunk
-    for i in range(lo, hi, chunk):
-        j = min(hi, i + chunk)
-        p = _sample_passes(models, args, rays[i:j], None if ts is None else ts[i:j], "test", None, None, None, apply_brdf,
-                           bTestNormal, False, False, apply_theta)
-        out, _, _, weights, depth, acc = _composite_merged(p, args)
+    for i, j in walk.chunks():
+        p, (out, _, _, weights, depth, acc) = _merged_geometry(models, args, rays[i:j], None if ts is None else ts[i:j],
+                                                               apply_brdf=apply_brdf, bTestNormal=bTestNormal, apply_theta=apply_theta)
         yield i, j, Surface(acc, weights.sum(-1), depth, rays[i:j, 3:6].float().contiguous(), p.model, args, p.spec, bool(apply_brdf),
                             bool(apply_theta), out.contiguous() if per_sample else None, weights.contiguous() if per_sample else None)
 
 
-def _join_surfaces(parts, models, args, rays, apply_brdf, apply_theta, bTestNormal, per_sample, group):
+def _join_surfaces(walk, parts, models, args, rays, apply_brdf, apply_theta, bTestNormal, per_sample):
     """One Surface of all rays from this rank's chunk surfaces (all-gathered along the ray axis under data parallelism)."""
-    from .distributed import gather_rows, world_info
     model = models["coarse"]
-    _, world = world_info(group)
-    if parts:
-        spec = parts[0].spec
-    else:                       # a rank without rays (more ranks than rays): the spec is still the model's
-        nr_lr = model.normal in ("analystic_learned", "learned")
-        nr_an = model.normal in ("analystic_learned", "analystic") or bTestNormal
-        spec = model.spec(apply_brdf, apply_theta, nr_lr, nr_an)
-    C, SG = spec.out_channels, args.n_samples + args.guided_samples
-    shapes = {"acc": (0, C), "wsum": (0,), "depth": (0,)}
-    if per_sample:
-        shapes.update(rows=(0, SG, C), weights=(0, SG))
-    res = {}
-    for k, shape in shapes.items():
-        v = [getattr(c, k) for c in parts]
-        t = torch.cat(v, 0) if v else torch.zeros(shape, dtype=torch.float32, device=rays.device)
-        res[k] = (gather_rows(t, group) if world > 1 else t).contiguous()
+    # a rank without rays (more ranks than rays): the spec is still the model's
+    spec = parts[0].spec if parts else _field_spec(model, apply_brdf, apply_theta, bTestNormal)
+    res = walk.join_attrs(parts, Surface.row_table(spec, args, per_sample), rays.device)
     return Surface(res["acc"], res["wsum"], res["depth"], rays[:, 3:6].float().contiguous(), model, args, spec, bool(apply_brdf),
                    bool(apply_theta), res.get("rows"), res.get("weights"))
 
@@ -183,8 +171,7 @@ def relight(surface, sun_dirs, apply_brdf=None, cos_irra_on=False, out=None, vie
         raise ValueError(f"view_dirs ({view.shape[0]}) and sun_dirs ({K}) must pair up (or one of them be a single direction)")
     R = surface.n_rays
     desc = surface.desc(apply_brdf, cos_irra_on)
-    if out is not None and (tuple(out.shape) != (K, R, 3) or out.dtype != torch.float32):
-        raise ValueError(f"out must be float32 {(K, R, 3)}, got {out.dtype} {tuple(out.shape)}")
+    check_out(out, (K, R, 3))
     from . import _lib as L
     samples = surface.per_sample and desc.kind != L.BN_SHADE_LAMBERT
     # the per-sample kernel writes through a plane stride: the (K, i:j, 3) slice of a whole view is written in place
@@ -224,39 +211,22 @@ def relight_image(models, args, rays, sun_dirs, ts=None, chunk=None, apply_brdf=
         if return_surface:
             res["surface"] = surface
         return res
-    from .distributed import gather_rows, shard_bounds, world_info
     gsam_only, bTestNormal = kw.pop("gsam_only", False), kw.pop("bTestNormal", False)
     if kw:
         raise TypeError(f"relight_image: unexpected arguments {sorted(kw)}")
     _check_relightable(models["coarse"], args, gsam_only, True)
-    dev = rays.device
-    sun = _dirs(sun_dirs, dev)
-    K, R = sun.shape[0], rays.shape[0]
-    if out is not None and (tuple(out.shape) != (K, R, 3) or out.dtype != torch.float32):
-        raise ValueError(f"out must be float32 {(K, R, 3)}, got {out.dtype} {tuple(out.shape)}")
-    rank, world = world_info(group)
-    lo, hi = shard_bounds(R, rank, world)
-    # this rank's rays are shaded into `mine` (K, hi - lo, 3): the result itself on one rank, else gathered along the ray axis
-    if world == 1:
-        mine = out = torch.empty((K, R, 3), dtype=torch.float32, device=dev) if out is None else out
-    else:
-        mine = torch.empty((K, hi - lo, 3), dtype=torch.float32, device=dev)
+    sun = _dirs(sun_dirs, rays.device)
+    walk = ViewWalk(rays.shape[0], chunk or args.chunk, group)
+    rgb = walk.planes(sun.shape[0], (3,), out, rays.device)        # this rank's rays are shaded straight into it
     kept, depth = [], []
-    for i, j, part in _surface_chunks(models, args, rays, ts, chunk, apply_brdf, apply_theta, group, bTestNormal, True):
-        relight(part, sun, apply_brdf=apply_brdf, cos_irra_on=cos_irra_on, out=mine[:, i - lo:j - lo])
+    for i, j, part in _surface_chunks(walk, models, args, rays, ts, apply_brdf, apply_theta, bTestNormal, True):
+        relight(part, sun, apply_brdf=apply_brdf, cos_irra_on=cos_irra_on, out=rgb.chunk(i, j))
         depth.append(part.depth)
         if return_surface:
             kept.append(part)
-    if world > 1:
-        rgb = gather_rows(mine.transpose(0, 1).contiguous(), group).transpose(0, 1)          # (R, K, 3) rows in rank order
-        if out is None:
-            out = rgb.contiguous()
-        else:
-            out.copy_(rgb)
-    d = torch.cat(depth, 0) if depth else torch.zeros((0,), dtype=torch.float32, device=dev)
-    res = {"rgb": out, "depth": gather_rows(d, group) if world > 1 else d}
+    res = {"rgb": rgb.result(), "depth": walk.join(depth, (), device=rays.device)}
     if return_surface:
-        res["surface"] = _join_surfaces(kept, models, args, rays, apply_brdf, apply_theta, bTestNormal, True, group)
+        res["surface"] = _join_surfaces(walk, kept, models, args, rays, apply_brdf, apply_theta, bTestNormal, True)
     return res
 
 

@@ -308,6 +308,12 @@ def identity_desc(C, lambda_rgb=1.0, lambda_ds=0.0, lambda_hs=0.0, usealldepth=F
     return d
 
 
+def _field_spec(model, apply_brdf, apply_theta, bTestNormal=False):
+    """The spec render_rays evaluates the field with: the heads of the shading and the model's normals (bTestNormal: the analytic too)."""
+    return model.spec(apply_brdf, apply_theta, model.normal in ("analystic_learned", "learned"),
+                      model.normal in ("analystic_learned", "analystic") or bTestNormal)
+
+
 def _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, target_std, apply_brdf, bTestNormal, bTestSun_v,
                    gsam_only, apply_theta, defer_sun=False):
     """render_rays up to the final compositing: pass 1, the optional sun-visibility pass and the guided samples, with every
@@ -335,10 +341,7 @@ def _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, tar
     near, far = rays[:, 6:7], rays[:, 7:8]
     rays_d = rays[:, 3:6]
     sun_d = rays[:, 8:11] if args.data == "sat" else torch.ones_like(rays[:, 0:3])
-
-    nr_lr = model.normal in ("analystic_learned", "learned")
-    nr_an = model.normal in ("analystic_learned", "analystic") or bTestNormal
-    spec = model.spec(apply_brdf, apply_theta, nr_lr, nr_an)
+    spec = _field_spec(model, apply_brdf, apply_theta, bTestNormal)
     packed = model.repack(spec)
     rays_t = None
     if model.beta:                              # rendering.py:226-229
@@ -413,20 +416,32 @@ def _composite_merged(p, args):
     return (out,) + tuple(Fn.composite(p.z_all, out, noise2 if args.noise_std != 0 else None, args.noise_std))
 
 
+def _merged_geometry(models, args, rays, ts=None, *, mode="test", valid_depth=None, target_depths=None, target_std=None,
+                    apply_brdf=False, bTestNormal=False, bTestSun_v=False, apply_theta=False):
+    """The geometry of one chunk of rays on the merged S + G sample set, everything of render_rays before the shading:
+    _sample_passes (its draws first), then _composite_merged (its randn).  render_rays shades the result; relight keeps the
+    sums and maps.view_maps reduces the per-sample tensors, so after the same torch.manual_seed all three hold the same bits.
+    -> (p, (out, alphas, transparency, weights, depth, acc))."""
+    p = _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, target_std, apply_brdf, bTestNormal, bTestSun_v,
+                       False, apply_theta)
+    return p, _composite_merged(p, args)
+
+
 def render_rays(models, args, rays, ts, mode="test", valid_depth=None, target_depths=None, target_std=None,
                 apply_brdf=False, print_debuginfo=False, bTestNormal=False, bTestSun_v=False, gsam_only=False, rows=None,
                 cols=None, percent=0, apply_theta=False, cos_irra_on=False):
     """render_rays, spsbrdf-nerf branch (rendering.py:168-291)."""
-    p = _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, target_std, apply_brdf, bTestNormal, bTestSun_v,
-                       gsam_only, apply_theta)
-    model, spec = p.model, p.spec
     if gsam_only:
-        result, brdf_type = inference(model, args, None, p.z2, rays_d=p.rays_d, sun_d=p.sun_d, rays_t=p.rays_t, z_vals_unsort=p.z2,
-                                      apply_brdf=apply_brdf, bTestNormal=bTestNormal, sun_res=p.sun_res, sort_idx=None, mode=mode,
-                                      apply_theta=apply_theta, cos_irra_on=cos_irra_on, _rays=p.rays, _packed=p.packed, rows=rows, cols=cols)
+        p = _sample_passes(models, args, rays, ts, mode, valid_depth, target_depths, target_std, apply_brdf, bTestNormal, bTestSun_v,
+                           True, apply_theta)
+        result, brdf_type = inference(p.model, args, None, p.z2, rays_d=p.rays_d, sun_d=p.sun_d, rays_t=p.rays_t, z_vals_unsort=p.z2,
+                                      apply_brdf=apply_brdf, bTestNormal=bTestNormal, sun_res=p.sun_res, sort_idx=None, mode=mode, rows=rows,
+                                      apply_theta=apply_theta, cos_irra_on=cos_irra_on, _rays=p.rays, _packed=p.packed, cols=cols)
         return {f"{k}_coarse": v for k, v in result.items()}, brdf_type
+    p, (out, alphas, transparency, weights, depth, acc) = _merged_geometry(
+        models, args, rays, ts, mode=mode, valid_depth=valid_depth, target_depths=target_depths, target_std=target_std,
+        apply_brdf=apply_brdf, bTestNormal=bTestNormal, bTestSun_v=bTestSun_v, apply_theta=apply_theta)
     z_unsort = torch.cat([p.z_vals, p.z2], -1)
-    out, alphas, transparency, weights, depth, acc = _composite_merged(p, args)
-    result, brdf_type = shade(model, args, spec, out, p.z_all, alphas, transparency, weights, depth, acc, p.rays_d, p.sun_d, apply_brdf,
+    result, brdf_type = shade(p.model, args, p.spec, out, p.z_all, alphas, transparency, weights, depth, acc, p.rays_d, p.sun_d, apply_brdf,
                               cos_irra_on, p.idx, z_unsort, rows=rows, cols=cols)
     return {f"{k}_coarse": v for k, v in result.items()}, brdf_type

@@ -19,7 +19,8 @@ import torch
 
 from . import functions as Fn
 from .relight import _TILE_BYTES, _dirs       # (the package binds the name `relight` to the function: import by module path)
-from .rendering import _sample_passes, shade_desc
+from .rendering import _field_spec, _sample_passes, shade_desc
+from .viewwalk import ViewWalk, check_out
 
 
 def _check_shadowed(model, args, apply_brdf):
@@ -60,6 +61,13 @@ class ShadowSurface:
     def rays_d(self):
         return self.rays[:, 3:6]
 
+    @staticmethod
+    def row_table(spec, args, per_sample, W):
+        """(attribute, trailing shape) of the per-ray tensors that ViewWalk.join_attrs joins; W: the columns of the ray table."""
+        C, G = spec.out_channels, args.guided_samples
+        return ([("acc", (C,)), ("wsum", ()), ("depth", ()), ("rays", (W,)), ("d1", ()), ("u_sun", (G,))]
+                + ([("noise_sun", (G,))] if args.noise_std != 0 else []) + ([("rows", (G, C)), ("weights", (G,))] if per_sample else []))
+
     def desc(self, cos_irra_on=False):
         """bn_shade_desc of this surface (the selection rules of rendering.shade(), apply_brdf=True)."""
         return shade_desc(self.model, self.args, self.spec, True, cos_irra_on)
@@ -72,15 +80,10 @@ def _per_sample(model, args, spec):
     return shade_desc(model, args, spec, True, False).kind == L.BN_SHADE_LAMBERT or bool(model.MultiBRDF)
 
 
-def _shadow_chunks(models, args, rays, ts, chunk, apply_theta, group, bTestNormal):
+def _shadow_chunks(walk, models, args, rays, ts, apply_theta, bTestNormal):
     """The geometry of this rank's share of the rays, chunk by chunk: yields (i, j, ShadowSurface of rays[i:j])."""
-    from .distributed import shard_bounds, world_info
-    rank, world = world_info(group)
-    lo, hi = shard_bounds(rays.shape[0], rank, world)
-    chunk = chunk or args.chunk
     noise_on = args.noise_std != 0
-    for i in range(lo, hi, chunk):
-        j = min(hi, i + chunk)
+    for i, j in walk.chunks():
         # rand (R, S), randn (R, S), the sun pass's rand (R, G) and randn (R, G), rand (R, G): render_rays' order
         p = _sample_passes(models, args, rays[i:j], None if ts is None else ts[i:j], "test", None, None, None, True, bTestNormal,
                            False, True, apply_theta, defer_sun=True)
@@ -102,34 +105,15 @@ def render_shadow_surface(models, args, rays, ts=None, chunk=None, apply_brdf=Tr
     samples, pass 2 on the G guided samples and its compositing - WITHOUT the sun pass and the shading.  Every random draw is taken
     in render_rays' order (the sun pass's two included), so after the same torch.manual_seed `depth` is its depth_coarse bit for
     bit.  Under data parallelism every rank renders its contiguous share and the rows are all-gathered.  -> ShadowSurface."""
-    from .distributed import gather_rows, shard_bounds, world_info
     model = models["coarse"]
     _check_shadowed(model, args, apply_brdf)
-    parts = [c for _, _, c in _shadow_chunks(models, args, rays, ts, chunk, apply_theta, group, bTestNormal)]
-    _, world = world_info(group)
-    chunk = chunk or args.chunk
-    bounds = []
-    for r in range(world):
-        lo, hi = shard_bounds(rays.shape[0], r, world)
-        bounds += [(i, min(hi, i + chunk)) for i in range(lo, hi, chunk)]
-    nr_lr = model.normal in ("analystic_learned", "learned")
-    nr_an = model.normal in ("analystic_learned", "analystic") or bTestNormal
-    spec = parts[0].spec if parts else model.spec(True, apply_theta, nr_lr, nr_an)
+    walk = ViewWalk(rays.shape[0], chunk or args.chunk, group)
+    parts = [c for _, _, c in _shadow_chunks(walk, models, args, rays, ts, apply_theta, bTestNormal)]
+    spec = parts[0].spec if parts else _field_spec(model, True, apply_theta, bTestNormal)
     packed = parts[0].packed if parts else model.repack(spec)
-    C, G, W = spec.out_channels, args.guided_samples, rays.shape[1]
-    keep = _per_sample(model, args, spec)
-    shapes = {"acc": (0, C), "wsum": (0,), "depth": (0,), "rays": (0, W), "d1": (0,), "u_sun": (0, G)}
-    if args.noise_std != 0:
-        shapes["noise_sun"] = (0, G)
-    if keep:
-        shapes.update(rows=(0, G, C), weights=(0, G))
-    res = {}
-    for k, shape in shapes.items():
-        v = [getattr(c, k) for c in parts]
-        t = torch.cat(v, 0) if v else torch.zeros(shape, dtype=torch.float32, device=rays.device)
-        res[k] = (gather_rows(t, group) if world > 1 else t).contiguous()
+    res = walk.join_attrs(parts, ShadowSurface.row_table(spec, args, _per_sample(model, args, spec), rays.shape[1]), rays.device)
     return ShadowSurface(res["acc"], res["wsum"], res["depth"], res["rays"], res["d1"], res["u_sun"], res.get("noise_sun"), model, args,
-                         spec, packed, bool(apply_theta), res.get("rows"), res.get("weights"), bounds)
+                         spec, packed, bool(apply_theta), res.get("rows"), res.get("weights"), walk.all_chunks())
 
 
 def _sun_pass(surface, sun, desc, rgb, vis, dir_tile):
@@ -186,8 +170,7 @@ def relight_shadowed(surface, sun_dirs, cos_irra_on=False, out=None, dir_tile=No
     dev = surface.acc.device
     sun = _dirs(sun_dirs, dev)
     K, R = sun.shape[0], surface.n_rays
-    if out is not None and (tuple(out.shape) != (K, R, 3) or out.dtype != torch.float32):
-        raise ValueError(f"out must be float32 {(K, R, 3)}, got {out.dtype} {tuple(out.shape)}")
+    check_out(out, (K, R, 3))
     desc = surface.desc(cos_irra_on)
     direct = out is None or (out.is_cuda and Fn.plane_rows(out))
     rgb = out if (direct and out is not None) else torch.empty((K, R, 3), dtype=torch.float32, device=dev)
@@ -221,47 +204,30 @@ def relight_image_shadowed(models, args, rays, sun_dirs, ts=None, chunk=None, ap
     cos_irra_on and a normal field the sun pass is unused upstream and is not run: visibility is None unless
     want_visibility=True asks for the map (want_visibility=False: never computed).  Under data parallelism each rank takes its
     contiguous share and the results are all-gathered."""
-    from .distributed import gather_rows, shard_bounds, world_info
     model = models["coarse"]
     _check_shadowed(model, args, apply_brdf)
     dev = rays.device
     sun = _dirs(sun_dirs, dev)
-    K, R = sun.shape[0], rays.shape[0]
-    if out is not None and (tuple(out.shape) != (K, R, 3) or out.dtype != torch.float32):
-        raise ValueError(f"out must be float32 {(K, R, 3)}, got {out.dtype} {tuple(out.shape)}")
-    rank, world = world_info(group)
-    lo, hi = shard_bounds(R, rank, world)
-    if world == 1:
-        mine = out = torch.empty((K, R, 3), dtype=torch.float32, device=dev) if out is None else out
-    else:
-        mine = torch.empty((K, hi - lo, 3), dtype=torch.float32, device=dev)
-    vis, depth = None, []
-    for i, j, part in _shadow_chunks(models, args, rays, ts, chunk, apply_theta, group, bTestNormal):
+    K = sun.shape[0]
+    walk = ViewWalk(rays.shape[0], chunk or args.chunk, group)
+    rgb, vis, depth = walk.planes(K, (3,), out, dev), None, []
+    for i, j, part in _shadow_chunks(walk, models, args, rays, ts, apply_theta, bTestNormal):
         if want_visibility is None:
             want_visibility = not (cos_irra_on and part.desc(False).ch_normal >= 0)
         if want_visibility and vis is None:
-            vis = torch.empty((K, hi - lo), dtype=torch.float32, device=dev)
-        got = relight_shadowed(part, sun, cos_irra_on=cos_irra_on, out=mine[:, i - lo:j - lo], dir_tile=dir_tile,
+            vis = walk.planes(K, (), None, dev)
+        got = relight_shadowed(part, sun, cos_irra_on=cos_irra_on, out=rgb.chunk(i, j), dir_tile=dir_tile,
                                want_visibility=bool(want_visibility))
         if want_visibility:
-            vis[:, i - lo:j - lo] = got[1]
+            vis.chunk(i, j).copy_(got[1])
         depth.append(part.depth)
-    if want_visibility and vis is None:                      # a rank without rays
-        vis = torch.empty((K, 0), dtype=torch.float32, device=dev)
-    if world > 1:
-        rgb = gather_rows(mine.transpose(0, 1).contiguous(), group).transpose(0, 1)          # (R, K, 3) rows in rank order
-        if out is None:
-            out = rgb.contiguous()
-        else:
-            out.copy_(rgb)
-        if want_visibility is None:                          # a rank without rays: as the ranks with rays decide
-            nr = model.normal in ("analystic_learned", "analystic", "learned") or bTestNormal
-            want_visibility = not (cos_irra_on and nr)
-            vis = torch.empty((K, 0), dtype=torch.float32, device=dev) if want_visibility else None
-        if vis is not None:
-            vis = gather_rows(vis.transpose(0, 1).contiguous(), group).transpose(0, 1).contiguous()
-    d = torch.cat(depth, 0) if depth else torch.zeros((0,), dtype=torch.float32, device=dev)
-    return {"rgb": out, "depth": gather_rows(d, group) if world > 1 else d, "visibility": vis}
+    if want_visibility is None and walk.world > 1:           # a rank without rays: as the ranks with rays decide
+        nr = model.normal in ("analystic_learned", "analystic", "learned") or bTestNormal
+        want_visibility = not (cos_irra_on and nr)
+    if want_visibility and vis is None:                      # a rank without rays takes part in the gather with zero rays
+        vis = walk.planes(K, (), None, dev)
+    rgb, vis = rgb.result(), None if vis is None else vis.result()
+    return {"rgb": rgb, "depth": walk.join(depth, (), device=dev), "visibility": vis}
 
 
 __all__ = ["ShadowSurface", "render_shadow_surface", "sun_visibility", "relight_shadowed", "relight_image_shadowed"]
