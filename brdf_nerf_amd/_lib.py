@@ -66,6 +66,14 @@ BN_SSIM_MAX_WINDOW = 11
 BN_NCC_MAX_RANGE, BN_NCC_MAX_SCALE, BN_NCC_MAX_SHIFT, BN_NCC_MAX_CELLS = 8, 16, 1 << 20, 1 << 22
 BN_FILL_MAX_SIDE = 8192
 BN_MAPS_MAX_SAMPLES, BN_MAPS_MAX_CHANNELS = 4096, 64
+BN_RPC_NEWTON_ITERS = 8
+BN_CS_ECEF, BN_CS_UTM = 0, 1
+
+
+class Rpc(C.Structure):               # bn_rpc: 90 doubles
+    _fields_ = [(k, C.c_double) for k in ("row_offset", "col_offset", "lat_offset", "lon_offset", "alt_offset", "row_scale",
+                                          "col_scale", "lat_scale", "lon_scale", "alt_scale")] + \
+               [(k, C.c_double * 20) for k in ("row_num", "row_den", "col_num", "col_den")]
 
 
 class NormalReg(C.Structure):         # bn_normal_reg
@@ -174,6 +182,12 @@ _SIGS = {
     "bn_ray_maps": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int64, C.c_int64, C.c_int64, C.c_int32, fptr, C.c_int64, C.c_int64, C.c_int32,
                               C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),
     "bn_point_normals": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_int32, fptr, fptr, fptr, fptr]),
+    "bn_rpc_project": (C.c_int, [C.POINTER(Rpc), fptr, fptr, fptr, C.c_int64, fptr, fptr, fptr]),
+    "bn_rpc_localize": (C.c_int, [C.POINTER(Rpc), fptr, fptr, C.c_int32, C.c_int64, C.c_int64, C.c_double, fptr, fptr, fptr]),
+    "bn_geo_world": (C.c_int, [fptr, fptr, C.c_int64, C.c_int32, C.c_int32, C.c_int32, fptr, fptr]),
+    "bn_rpc_rays": (C.c_int, [C.POINTER(Rpc), fptr, fptr, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                              C.c_int32, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_float), C.c_int32, fptr, C.c_int64, fptr,
+                              fptr, fptr, fptr]),
     "bn_lambert_tail": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, fptr, fptr, C.c_int64, fptr,
                                   C.c_int64, fptr, C.c_int64, fptr, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, fptr, fptr,
                                   C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),

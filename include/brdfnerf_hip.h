@@ -696,6 +696,78 @@ int bn_ray_maps(const float *z, const float *w, const float *depth, const float 
                 float *surf, float *var, float *std, float *accum, long long *counters, void *stream);
 int bn_point_normals(const double *points, int32_t H, int32_t W, int32_t round_f32, const float *valid_in, float *normals,
                      float *valid_out, void *stream);
+/* The rays of a satellite view from its RPC camera model (additive to ABI 7): get_rays, normalize_rays and the localisation they
+ * call (datasets/satellite_rgb_dep.py:23-78, 550-559), per pixel, in float64 with EVERY operation rounded on its own (camera.hip
+ * is compiled with fp contraction off).  Only + - x / and sqrt occur up to the geodetic point; both are correctly rounded on the
+ * device, so that part is a pure function of its inputs and is held to a numpy statement bit for bit.
+ *
+ * The descriptor: 90 doubles, the keys of the `rpc` dictionary of a scene's JSON.  The 20 coefficients of a polynomial follow
+ * the RPC00B order; with L, P, H the normalised longitude, latitude and altitude the monomials are, each product formed left
+ * to right as written:
+ *   m0 = 1      m1 = L        m2 = P        m3 = H        m4 = L P      m5 = L H      m6 = P H      m7 = L L      m8 = P P
+ *   m9 = H H    m10 = (P L) H m11 = m7 L    m12 = m4 P    m13 = m5 H    m14 = m7 P    m15 = m8 P    m16 = m6 H    m17 = m7 H
+ *   m18 = m8 H  m19 = m9 H
+ * A polynomial is s = c0; s = s + c_k m_k for k = 1 .. 19 ascending.  This is the public RPC00B definition; it was not checked
+ * against the rpcm package.
+ * 1. normalise    L = (lon - lon_offset) / lon_scale, P = (lat - lat_offset) / lat_scale, H = (alt - alt_offset) / alt_scale
+ * 2. project      col = (col_num.m / col_den.m) col_scale + col_offset ; row likewise
+ * 3. localise     pixel (col, row) at altitude alt: cn = (col - col_offset) / col_scale, rn = (row - row_offset) / row_scale,
+ *                 (L, P) = (0, 0), then BN_RPC_NEWTON_ITERS times, without a data-dependent exit:
+ *                   N, D the numerator and denominator of col, N_L, N_P, D_L, D_P their derivatives, formed from
+ *                     d m / d L: m1: 1, m4: P, m5: H, m7: 2 L, m10: m6, m11: 3 m7, m12: m8, m13: m9, m14: 2 m4, m17: 2 m5
+ *                     d m / d P: m2: 1, m4: L, m6: H, m8: 2 P, m10: m5, m12: 2 m4, m14: m7, m15: 3 m8, m16: m9, m18: 2 m6
+ *                   as s = c_k of the term whose derivative is 1, then s = s + c_k (d m_k) for the other terms, k ascending;
+ *                   fc = N / D - cn ; a = (N_L D - N D_L) / (D D) ; b = (N_P D - N D_P) / (D D) ; fr, c, d the same for the row;
+ *                   det = a d - b c ; L = L - (fc d - b fr) / det ; P = P - (a fr - fc c) / det
+ *                 lon = L lon_scale + lon_offset, lat = P lat_scale + lat_offset.  A pixel for which det == 0 in one of the
+ *                 iterations, or whose lon or lat is not finite, gives (NaN, NaN) and is counted.
+ * 4. world        cs BN_CS_ECEF: sat_utils.latlon_to_ecef_custom (:110-125) as written there: rlat = lat (pi / 180), rlon
+ *                 likewise, v = a / sqrt(1 - (e2 sin rlat) sin rlat), x = ((v + alt) cos rlat) cos rlon, y = ((v + alt) cos rlat)
+ *                 sin rlon, z = (v (1 - e2) + alt) sin rlat.
+ *                 cs BN_CS_UTM: the Krueger series to n^6 (Karney 2011, eq. 35) on WGS84, k0 = 0.9996, false easting 500000,
+ *                 central meridian 6 zone - 183; with t = sinh(e atanh(e sin rlat)), tau = sin rlat / cos rlat, tau' = tau sqrt(1 + t t) -
+ *                 t sqrt(1 + tau tau): xi' = atan2(tau', cos dlon), eta' = atanh(sin dlon / sqrt(1 + tau' tau')), and the six
+ *                 terms alpha_j sin(2 j (xi' + i eta')) summed by the angle-addition recurrence from sin / cos of 2 xi' and sinh /
+ *                 cosh of 2 eta'.  x = 500000 + k0 A eta, y = k0 A xi (+ 10,000,000 with south = 1), z = alt.  The zone is a
+ *                 parameter of the scene (upstream takes it from the first pixel of each call, sat_utils.py:156-159).  The
+ *                 device's float64 sin, cos, atanh, sinh, cosh and atan2 are not bit-specified: this step is held to the
+ *                 numpy statement within 1e-6 m, not bit for bit.  Not checked against pyproj.
+ * 5. ray          near = world point at max_alt, far = world point at min_alt ; d = far - near ; len = sqrt((d.x d.x + d.y d.y) +
+ *                 d.z d.z) ; dir = d / len.  round_f32 = 1 (upstream, :76-77 then :550-559): o32 = (float)near, the row is
+ *                 ((o32 - (float)center) / (float)range, (float)dir, 0, (float)len / (float)range), the subtraction and the
+ *                 divisions in float32 - at a UTM northing of 3.3e6 m the origin is on a 0.25 m lattice.  round_f32 = 0: the
+ *                 row is ((float)((near - center) / range), (float)dir, 0, (float)(len / range)), formed in float64.
+ *                 sun (HOST pointer, 3 floats, nullable): columns 8-10 of every row.  A ray whose near or far pixel is
+ *                 counted by step 3, or one of whose eight values is not finite, has NaN in its columns 0-7 and is counted once.
+ *
+ * rpc is a HOST pointer.  Grid mode (cols == NULL): ray r of [r0, r1) is pixel (col r % W, row r / W).  Array mode: (cols[r],
+ * rows[r]), float64 device arrays.  Outputs are indexed from r0: ray r writes row r - r0.  counts (device, the CALLER zeroes):
+ * counts[0] += the counted rows, one integer atomic per block; no float atomic anywhere.
+ *   bn_rpc_project   lon, lat, alt float64 [n] -> col, row float64 [n]  (step 2)
+ *   bn_rpc_localize  alt: one altitude for all -> lonlat float64 [r1 - r0][2]  (step 3)
+ *   bn_geo_world     lonlat float64 [n][2], alt -> xyz float64 [n][3]  (step 4)
+ *   bn_rpc_rays      steps 1-5 in one launch: rays float32 [r1 - r0] rows of ray_stride >= 8 (11 with sun) floats; lonlat_near /
+ *                    lonlat_far (nullable) float64 [r1 - r0][2], the geodetic points the rays were formed from.
+ * Refused (BN_EINVAL): NULL rpc or outputs (counts included), one of cols / rows without the other, r0 < 0, r0 > r1, n < 0, more
+ * than 2^30 rays, W < 1 in grid mode, another cs, zone outside [1, 60], south or round_f32 other than 0 or 1, a range that is
+ * not positive and finite, a centre or altitude that is not finite, a scale of zero (or a non-finite scale or offset) in the
+ * descriptor, a ray_stride below the columns written. */
+#define BN_RPC_NEWTON_ITERS 8
+enum { BN_CS_ECEF = 0, BN_CS_UTM = 1 };
+typedef struct {
+  double row_offset, col_offset, lat_offset, lon_offset, alt_offset, row_scale, col_scale, lat_scale, lon_scale, alt_scale;
+  double row_num[20], row_den[20], col_num[20], col_den[20];
+} bn_rpc;
+int bn_rpc_project(const bn_rpc *rpc, const double *lon, const double *lat, const double *alt, int64_t n, double *col, double *row,
+                   void *stream);
+int bn_rpc_localize(const bn_rpc *rpc, const double *cols, const double *rows, int32_t W, int64_t r0, int64_t r1, double alt,
+                    double *lonlat, unsigned long long *counts, void *stream);
+int bn_geo_world(const double *lonlat, const double *alt, int64_t n, int32_t cs, int32_t zone, int32_t south, double *xyz,
+                 void *stream);
+int bn_rpc_rays(const bn_rpc *rpc, const double *cols, const double *rows, int32_t W, int64_t r0, int64_t r1, double min_alt,
+                double max_alt, int32_t cs, int32_t zone, int32_t south, const double *center, double range, const float *sun,
+                int32_t round_f32, float *rays, int64_t ray_stride, double *lonlat_near, double *lonlat_far,
+                unsigned long long *counts, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
