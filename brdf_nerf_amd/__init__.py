@@ -18,7 +18,7 @@ from .register import register_xy, apply_registration, altitude_mae_xy  # noqa: 
 from .fill import fill_holes, apply_fill  # noqa: F401
 from .maps import ray_maps, point_normals, depth_normals, view_maps  # noqa: F401
 from . import camera  # noqa: F401
-from .camera import Rpc, view_rays, scene_bounds, ray_table, utm_zone, sun_direction  # noqa: F401
+from .camera import Rpc, view_rays, scene_bounds, ray_table, utm_zone, sun_direction, depth_priors, nearest_lines  # noqa: F401
 from ._lib import set_deterministic  # noqa: F401
 
 __all__ = ["SpSBRDFNeRF", "load_model", "render_rays", "inference", "get_z_vals", "cal_weight", "functions", "set_deterministic",
@@ -27,4 +27,5 @@ __all__ = ["SpSBRDFNeRF", "load_model", "render_rays", "inference", "get_z_vals"
            "dsm_image", "altitude_mae", "image_psnr", "image_ssim", "dsm_normals", "normal_angle_mae", "score_view",
            "register_xy", "apply_registration", "altitude_mae_xy", "fill_holes", "apply_fill",
            "ray_maps", "point_normals", "depth_normals", "view_maps",
-           "camera", "Rpc", "view_rays", "scene_bounds", "ray_table", "utm_zone", "sun_direction"]
+           "camera", "Rpc", "view_rays", "scene_bounds", "ray_table", "utm_zone", "sun_direction", "depth_priors",
+           "nearest_lines"]

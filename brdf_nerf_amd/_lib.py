@@ -188,6 +188,10 @@ _SIGS = {
     "bn_rpc_rays": (C.c_int, [C.POINTER(Rpc), fptr, fptr, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_int32,
                               C.c_int32, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_float), C.c_int32, fptr, C.c_int64, fptr,
                               fptr, fptr, fptr]),
+    "bn_tie_owner": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_int32, fptr, fptr, fptr]),
+    "bn_tie_priors": (C.c_int, [C.POINTER(Rpc), fptr, fptr, fptr, fptr] + [C.c_int32] * 5 + [fptr, fptr, C.c_double, C.c_double,
+                                C.c_double, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_int32] +
+                      [C.c_double] * 6 + [fptr] * 9),
     "bn_lambert_tail": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, fptr, fptr, C.c_int64, fptr,
                                   C.c_int64, fptr, C.c_int64, fptr, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, fptr, fptr,
                                   C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),

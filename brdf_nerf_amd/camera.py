@@ -12,7 +12,11 @@ include/brdfnerf_hip.h ("The rays of a satellite view") and runs in brdf_nerf_am
   geo_world          geodetic points -> ECEF (sat_utils.latlon_to_ecef_custom) or UTM (Krueger series to n^6) (bn_geo_world)
   view_rays          get_rays + normalize_rays + get_sun_dirs of one view in one launch per chunk (bn_rpc_rays)
   scene_bounds       init_scaling_params (:238-261): the scene.loc dictionary, the centre and the range
-  ray_table          the views of a scene concatenated into a RayTable (load_data, :311-394, without its file readers)
+  nearest_lines      the lines scale_depth (:396-399) samples: torch's nearest rule with its float32 scale, and its inverse
+  depth_priors       load_depth_data (:401-548) of one view from its tie points, paired by pixel: depths, weights, valid_depth,
+                     depth_std, the padded rays and the normals (bn_tie_owner, bn_tie_priors, one lane per tie point)
+  ray_table          the views of a scene concatenated into a RayTable (load_data, :311-394, and with priors= load_depth_data:
+                     load_train_split without its file readers)
   utm_zone           the zone of a point, with the Norway and Svalbard exceptions (utm.latlon_to_zone_number)
   sun_direction      get_sun_dirs (:561-576)
 
@@ -23,8 +27,9 @@ dsm.SceneFrame keeps refusing 'ecef'.  The UTM zone is a parameter of the scene,
 upstream does (sat_utils.py:156-159); south=False adds no false northing, which is what upstream's "+proj=utm +zone=17R" does in
 both hemispheres.
 
-Not here: the file readers (JSON, GeoTIFF), image scaling, the tie-point depth priors of load_depth_data, an inverse UTM.  The
-RPC rule is the public RPC00B definition and the UTM series Karney's; neither was checked against rpcm or pyproj.
+Not here: the file readers (JSON, GeoTIFF, the tie-point text files), image scaling, an inverse UTM
+(sat_utils.ecef_to_latlon_custom), a `group` for depth_priors (a view's priors are made once), the normals as a table column.
+The RPC rule is the public RPC00B definition and the UTM series Karney's; neither was checked against rpcm or pyproj.
 """
 import ctypes as C
 import math
@@ -337,17 +342,161 @@ def scene_bounds(views, cs="utm", zone=None, south=False, device=None, chunk=Non
     return loc, tuple(offset), max(scale)
 
 
+def nearest_lines(n, downscale):
+    """The lines a nearest resize of n lines by `downscale` samples (scale_depth, :396-399: torch's interpolate to the size
+    int(n / downscale), whose scale is the float32 quotient n / n_out): -> n_out, src int64 (n_out) with
+    src[j] = min(int(floorf((float)j * ((float)n / (float)n_out))), n - 1), dst int32 (n) its inverse, -1 where a line is not sampled."""
+    n = int(n)
+    if n < 1 or n > 1 << 24:
+        raise ValueError(f"nearest_lines: {n} lines (1 to 2^24: the float32 rule is exact in the index up to there)")
+    if not (math.isfinite(float(downscale)) and float(downscale) >= 1.0):
+        raise ValueError(f"nearest_lines: downscale {downscale} must be finite and at least 1")
+    n_out = int(n / downscale)
+    if n_out < 1:
+        raise ValueError(f"nearest_lines: {n} lines at downscale {downscale} leave none")
+    scale = np.float32(n) / np.float32(n_out)
+    src = np.minimum(np.floor(np.arange(n_out, dtype=np.float32) * scale).astype(np.int64), n - 1)
+    dst = np.full(n, -1, dtype=np.int32)
+    dst[src] = np.arange(n_out, dtype=np.int32)
+    return n_out, src, dst
+
+
+def _tie_inputs(name, pts2d, pts3d, correl, dev):
+    px = torch.as_tensor(pts2d)
+    if px.is_floating_point() or px.dtype == torch.bool or px.is_complex():
+        raise ValueError(f"{name}: pts2d are {px.dtype}: integer (col, row) pixels at full resolution")
+    px = px.reshape(-1, 2) if px.dim() == 1 and px.numel() == 2 else px             # one tie point, as np.loadtxt returns it
+    if px.dim() != 2 or px.shape[1] != 2:
+        raise ValueError(f"{name}: pts2d must be (T, 2), got {tuple(px.shape)}")
+    T = px.shape[0]
+    _check_count(T, name)
+    px = px.to(dev).to(torch.int64).clamp(-(1 << 31), (1 << 31) - 1).to(torch.int32).contiguous()
+    pts3d = torch.as_tensor(pts3d, dtype=torch.float64).to(dev).reshape(-1, 3).contiguous()
+    correl = torch.as_tensor(correl, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+    if pts3d.shape[0] != T or correl.shape[0] != T:
+        raise ValueError(f"{name}: {T} pixels, {pts3d.shape[0]} points and {correl.shape[0]} correlations")
+    return px, pts3d, correl, T
+
+
+@torch.no_grad()
+def tie_priors(rpc, H, W, pts2d, pts3d, correl, cmin, cmax, min_alt, max_alt, center, range=None, cs="utm", zone=None, south=False,
+               downscale=1.0, corrscale=1.0, stdscale=1.0, margin=0.0, std_span=0.0, precision="reference", want_rays=False,
+               want_points=True, want_tie_rays=False, device=None):
+    """The two launches of the depth priors (bn_tie_owner, bn_tie_priors) with the correlation bounds given: the raw buffers.
+    -> {"owner" int32 (H, W), "valid" (Hout Wout), "depths" (Hout Wout, 2), "depth_std", "rays" (Hout Wout, 8) or None, "points"
+    (H, W, 3) and "valid_full" (H, W) or None, "tie_rays" (T, 8) or None, "counts" int64 (4) on the device, "shape",
+    "src_rows", "src_cols" (int64, on the device)}.  depth_priors is the public form."""
+    name = "tie_priors"
+    if precision not in _PRECISION:
+        raise ValueError(f"{name}: unknown precision {precision!r} ('reference' or 'exact')")
+    code, zone, south = _world_args(cs, zone, south, rpc)
+    center, range = _frame(center, range, cs)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H * W > 1 << 30:
+        raise ValueError(f"{name}: a view of {H} x {W} pixels (at least 1 x 1, H W at most 2^30)")
+    scalars = {"min_alt": min_alt, "max_alt": max_alt, "cmin": cmin, "cmax": cmax, "corrscale": corrscale, "stdscale": stdscale,
+               "margin": margin, "std_span": std_span, "downscale": downscale}
+    for k, v in scalars.items():
+        if not math.isfinite(float(v)):
+            raise ValueError(f"{name}: {k} {v} must be finite")
+    if not float(cmax) > float(cmin):
+        raise ValueError(f"{name}: correlations [{cmin}, {cmax}]: cmax must exceed cmin")
+    dev = _device(device, pts2d, pts3d, correl)
+    px, pts3d, correl, T = _tie_inputs(name, pts2d, pts3d, correl, dev)
+    Hout, src_r, dst_r = nearest_lines(H, downscale)
+    Wout, src_c, dst_c = nearest_lines(W, downscale)
+    identity = float(downscale) == 1.0
+    dst_r, dst_c = (None, None) if identity else (torch.from_numpy(dst_r).to(dev), torch.from_numpy(dst_c).to(dev))
+    f32 = dict(dtype=torch.float32, device=dev)
+    owner = torch.full((H, W), -1, dtype=torch.int32, device=dev)
+    counts = torch.zeros((4,), dtype=torch.int64, device=dev)
+    out = {"owner": owner, "counts": counts, "shape": (Hout, Wout), "valid": torch.zeros((Hout * Wout,), **f32),
+           "depths": torch.zeros((Hout * Wout, 2), **f32), "depth_std": torch.zeros((Hout * Wout,), **f32),
+           "rays": torch.zeros((Hout * Wout, 8), **f32) if want_rays else None,
+           "points": torch.zeros((H, W, 3), **f32) if want_points else None,
+           "valid_full": torch.zeros((H, W), **f32) if want_points else None,
+           "tie_rays": torch.zeros((T, 8), **f32) if want_tie_rays else None,
+           "src_rows": torch.from_numpy(src_r).to(dev), "src_cols": torch.from_numpy(src_c).to(dev)}
+    c = (C.c_double * 3)(*center)
+    with torch.cuda.device(dev):
+        L.check(L.lib().bn_tie_owner(_p(px), T, H, W, _p(owner), _p(counts), _stream()), "bn_tie_owner")
+        L.check(L.lib().bn_tie_priors(rpc.ref(), _p(px), _p(owner), _p(pts3d), _p(correl), T, H, W, Hout, Wout, _p(dst_r), _p(dst_c),
+                                      float(downscale), float(min_alt), float(max_alt), code, zone, south, c, range,
+                                      _PRECISION[precision], float(cmin), float(cmax), float(corrscale), float(stdscale), float(margin),
+                                      float(std_span), _p(out["valid"]), _p(out["depths"]), _p(out["depth_std"]), _p(out["rays"]),
+                                      _p(out["points"]), _p(out["valid_full"]), _p(out["tie_rays"]), _p(counts), _stream()),
+                "bn_tie_priors")
+    return out
+
+
+@torch.no_grad()
+def depth_priors(rpc, H, W, pts2d, pts3d, correl, min_alt, max_alt, center, range=None, cs="utm", zone=None, south=False, downscale=1.0,
+                 corrscale=1.0, stdscale=1.0, margin=0.0, std_span=0.0, precision="reference", want_rays=False, want_normals=True,
+                 device=None):
+    """The depth priors of one view from its tie points: load_depth_data (datasets/satellite_rgb_dep.py:401-548) without its file
+    readers, paired by pixel (include/brdfnerf_hip.h, "The depth priors of a view").
+    H, W and pts2d (T, 2) integer (col, row): at FULL resolution; rpc: Rpc.from_dict(d, downscale); pts3d (T, 3) world points,
+    correl (T) their correlation scores; center, range: as view_rays.  corrscale, stdscale, margin: upstream's options of those
+    names; std_span: upstream's depth_max - depth_min, which is 0 (so its depth_std is identically zero).
+    The correlations are normalised by their amin / amax over all T tie points, read from the device as two scalars; a cmax <=
+    cmin or a non-finite one is a ValueError (upstream divides by zero).
+    -> {"depths" (Hout Wout, 2) = (depth, weight), "valid_depth", "depth_std", "normals" (Hout Wout, 3) and "valid_normal"
+    (want_normals), "rays" (Hout Wout, 8) (want_rays: upstream's all_deprays), "shape" (Hout, Wout), "outside", "duplicates",
+    "skipped", "unsampled", "kept"}, with kept + outside + duplicates + skipped + unsampled == T.
+    Where valid_depth == 0 the depth is the float32 of the float64 mean of the kept depths (padding, no loss reads it), weight
+    and std are 0.  Normals: point_normals on the FULL-resolution grid of tie points (calc_normal_from_pts3d with its valid_depth
+    rule), (0, 0, 1) where valid_normal == 0 (:511-514), then the lines the resize samples.  At downscale == 1 every output is
+    upstream's; at other factors upstream raises (valid_depth.reshape(height, width) after scale_depth) and the outputs are
+    this project's reading of it: the resize of the full-resolution maps."""
+    from . import functions as Fn
+    name = "depth_priors"
+    dev = _device(device, pts2d, pts3d, correl)
+    pts2d, pts3d, cor, T = _tie_inputs(name, pts2d, pts3d, correl, dev)          # on the device once; tie_priors takes them as they are
+    if T == 0:
+        raise ValueError(f"{name}: no tie points (a view without priors: ray_table(priors=[..., None, ...]))")
+    cmin, cmax = torch.stack([cor.amin(), cor.amax()]).tolist()
+    if not (math.isfinite(cmin) and math.isfinite(cmax) and cmax > cmin):
+        raise ValueError(f"{name}: correlations in [{cmin}, {cmax}]: they must be finite and not all equal")
+    raw = tie_priors(rpc, H, W, pts2d, pts3d, cor, cmin, cmax, min_alt, max_alt, center, range, cs=cs, zone=zone, south=south,
+                     downscale=downscale, corrscale=corrscale, stdscale=stdscale, margin=margin, std_span=std_span,
+                     precision=precision, want_rays=want_rays, want_points=want_normals, device=dev)
+    valid, depths = raw["valid"], raw["depths"]
+    kept_t = valid.sum(dtype=torch.float64)
+    mean = (depths[:, 0].double().sum() / kept_t.clamp(min=1.0)).float()            # the invalid entries are zero
+    depths[:, 0] = torch.where(valid > 0, depths[:, 0], mean)
+    outside, duplicates, skipped, unsampled = raw["counts"].tolist()
+    res = {"depths": depths, "valid_depth": valid, "depth_std": raw["depth_std"], "shape": raw["shape"], "outside": outside,
+           "duplicates": duplicates, "skipped": skipped, "unsampled": unsampled, "kept": int(kept_t.item())}
+    if want_rays:
+        res["rays"] = raw["rays"]
+    if want_normals:
+        normals, valid_normal = Fn.point_normals(raw["points"].double(), raw["valid_full"], _PRECISION[precision] == 1)
+        up = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float32, device=dev)
+        normals = torch.where(valid_normal[..., None] > 0, normals, up)
+        rows, cols = raw["src_rows"], raw["src_cols"]
+        res["normals"] = normals[rows][:, cols].reshape(-1, 3).contiguous()
+        res["valid_normal"] = valid_normal[rows][:, cols].reshape(-1).contiguous()
+    return res
+
+
 @torch.no_grad()
 def ray_table(views, images, center, range=None, cs="utm", zone=None, south=False, precision="reference", device=None, seed=0,
-              chunk=None):
-    """The views of a scene as one RayTable without depth columns (load_data, :311-394): views as scene_bounds takes them, each
-    with "sun": (elevation_deg, azimuth_deg); images: per view the (H W, 3) colours, row-major.  cs='utm' without a zone: the
-    zone of the first view's lat / lon offset."""
+              chunk=None, priors=None, corrscale=1.0, stdscale=1.0, margin=1e-4, std_span=0.0):
+    """The views of a scene as one RayTable (load_data, :311-394, and with `priors` load_depth_data, :401-548: the whole of
+    load_train_split without the file readers): views as scene_bounds takes them, each with "sun": (elevation_deg, azimuth_deg);
+    images: per view the (H W, 3) colours, row-major.  cs='utm' without a zone: the zone of the first view's lat / lon offset.
+    priors: per view None or {"pts2d", "pts3d", "correl"} (depth_priors; corrscale, stdscale, margin - upstream's --margin
+    1e-4 - and std_span are its parameters): the table gains depths, valid_depth and depth_std, a view with None has
+    valid_depth = 0 rows.  A view's "H", "W" are its ray grid - the image AFTER its "downscale"; the tie points of a downscaled
+    view are at full resolution, which the view names as "full_H", "full_W" (their resize must be H x W).  priors=None: the
+    table without depth columns."""
     from .raytable import RayTable
     if len(views) != len(images) or not views:
         raise ValueError(f"ray_table: {len(views)} views and {len(images)} images")
-    tables = []
-    for v, img in zip(views, images):
+    if priors is not None and len(priors) != len(views):
+        raise ValueError(f"ray_table: {len(views)} views and {len(priors)} priors")
+    tables, cols = [], {"depths": [], "valid_depth": [], "depth_std": []}
+    for i, (v, img) in enumerate(zip(views, images)):
         rpc, H, W, min_alt, max_alt = _view_args(v)
         if cs == "utm" and zone is None:
             zone = utm_zone(rpc.lat_offset, rpc.lon_offset)
@@ -356,9 +505,32 @@ def ray_table(views, images, center, range=None, cs="utm", zone=None, south=Fals
         rays, _ = view_rays(rpc, H, W, min_alt, max_alt, center, range, cs=cs, zone=zone, south=south, sun=v["sun"], chunk=chunk,
                             precision=precision, device=device)
         tables.append(rays)
+        if priors is None:
+            continue
+        if priors[i] is None:
+            pr = {"depths": torch.zeros((H * W, 2), device=rays.device), "valid_depth": torch.zeros((H * W,), device=rays.device),
+                  "depth_std": torch.zeros((H * W,), device=rays.device)}
+        else:
+            missing = [k for k in ("pts2d", "pts3d", "correl") if k not in priors[i]]
+            if missing:
+                raise ValueError(f"ray_table: the priors of view {i} lack {missing}")
+            down = float(v.get("downscale", 1.0))
+            if down != 1.0 and not ("full_H" in v and "full_W" in v):
+                raise ValueError(f"ray_table: view {i} is downscaled by {down}: its priors need full_H and full_W")
+            pr = depth_priors(rpc, int(v.get("full_H", H)), int(v.get("full_W", W)), priors[i]["pts2d"], priors[i]["pts3d"],
+                              priors[i]["correl"], min_alt, max_alt, center, range, cs=cs, zone=zone, south=south, downscale=down,
+                              corrscale=corrscale, stdscale=stdscale, margin=margin, std_span=std_span, precision=precision,
+                              want_normals=False, device=rays.device)
+            if pr["shape"] != (H, W):
+                raise ValueError(f"ray_table: the priors of view {i} come out {pr['shape'][0]} x {pr['shape'][1]}, its rays are {H} x {W}")
+        for k in cols:
+            cols[k].append(pr[k])
     rays = torch.cat(tables, 0)
     rgbs = torch.cat([torch.as_tensor(img).to(rays.device).float() for img in images], 0)
-    return RayTable(rays, rgbs, device=rays.device, seed=seed)
+    if priors is None:
+        return RayTable(rays, rgbs, device=rays.device, seed=seed)
+    return RayTable(rays, rgbs, **{k: torch.cat(v, 0) for k, v in cols.items()}, device=rays.device, seed=seed)
 
 
-__all__ = ["Rpc", "utm_zone", "sun_direction", "project", "localize", "geo_world", "view_rays", "scene_bounds", "ray_table"]
+__all__ = ["Rpc", "utm_zone", "sun_direction", "project", "localize", "geo_world", "view_rays", "scene_bounds", "ray_table",
+           "nearest_lines", "tie_priors", "depth_priors"]

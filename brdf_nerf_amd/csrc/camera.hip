@@ -24,6 +24,13 @@
 // registers (142 VGPRs, 3 waves per SIMD); one set at a time the ray kernel takes 101 VGPRs, no scratch, 4 waves per SIMD.
 // A counted row (zero determinant, non-finite result) is summed per block and added with ONE integer atomic; there
 // is no float atomic in this file.
+//
+// The tie-point depth priors ("The depth priors of a view" in the header; load_depth_data, datasets/satellite_rgb_dep.py:401-548)
+// run the same ray chain (ray_chain below: ONE statement, called by both kernels) for the tie points of a view, one lane per tie
+// point: a view has far fewer tie points than pixels, so a lane per output pixel would leave most lanes idle.  Ownership of a
+// pixel is an integer atomicMax of the tie index in a launch of its own; the second launch works for the owners only and
+// scatters through inverse index vectors of the resize made on the host.  tie_priors_kernel: 109 VGPRs, no scratch, 4 waves per
+// SIMD (the eight ray values stay live across the point arithmetic); rpc_rays_kernel keeps its 101.
 #include <cmath>
 #include "common.h"
 #include "brdfnerf_hip.h"
@@ -220,11 +227,51 @@ void geo_world_kernel(const World Wd, const double *__restrict__ lonlat, const d
   xyz[3 * i + 2] = z;
 }
 
+// the scene's normalisation and the altitude bounds of a view: what the ray chain reads besides the pixel
+struct Frame {
+  int32_t round_f32;
+  double min_alt, max_alt, cx, cy, cz, range;
+};
+
+// step 5 of the header for one pixel: the eight values of the ray row into v (as computed, NOT yet NaN where counted) and the
+// geodetic near / far points.  -> true when the ray is counted.  The one statement of the chain: rpc_rays_kernel and
+// tie_priors_kernel both call it.
+__device__ __forceinline__ bool ray_chain(const bn_rpc &R, const World &Wd, const Frame &F, double col, double row, float (&v)[8],
+                                          double &lon_n, double &lat_n, double &lon_f, double &lat_f) {
+  bool bad = localize(R, col, row, F.max_alt, lon_n, lat_n);
+  bad = localize(R, col, row, F.min_alt, lon_f, lat_f) || bad;
+  double nx, ny, nz, fx, fy, fz;
+  geo_world(Wd, lon_n, lat_n, F.max_alt, nx, ny, nz);
+  geo_world(Wd, lon_f, lat_f, F.min_alt, fx, fy, fz);
+  const double dx = fx - nx, dy = fy - ny, dz = fz - nz;
+  const double len = sqrt((dx * dx + dy * dy) + dz * dz);
+  v[3] = (float)(dx / len);
+  v[4] = (float)(dy / len);
+  v[5] = (float)(dz / len);
+  v[6] = 0.f;
+  if (F.round_f32) {
+    const float rg = (float)F.range;
+    v[0] = ((float)nx - (float)F.cx) / rg;
+    v[1] = ((float)ny - (float)F.cy) / rg;
+    v[2] = ((float)nz - (float)F.cz) / rg;
+    v[7] = (float)len / rg;
+  } else {
+    v[0] = (float)((nx - F.cx) / F.range);
+    v[1] = (float)((ny - F.cy) / F.range);
+    v[2] = (float)((nz - F.cz) / F.range);
+    v[7] = (float)(len / F.range);
+  }
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) finite = finite && isfinite(v[i]);
+  return bad || !finite;
+}
+
 struct RayArgs {
   const double *cols, *rows;
-  int32_t W, round_f32, has_sun;
+  int32_t W, has_sun;
   int64_t r0, r1, ray_stride;
-  double min_alt, max_alt, cx, cy, cz, range;
+  Frame F;
   float sun[3];
   float *rays;
   double *lonlat_near, *lonlat_far;
@@ -238,8 +285,8 @@ void rpc_rays_kernel(const bn_rpc R, const World Wd, const RayArgs A) {
   if (r < A.r1) {
     double col, row, lon_n, lat_n, lon_f, lat_f;
     pixel_of(A.cols, A.rows, A.W, r, col, row);
-    bad = localize(R, col, row, A.max_alt, lon_n, lat_n);
-    bad = localize(R, col, row, A.min_alt, lon_f, lat_f) || bad;
+    float v[8];
+    bad = ray_chain(R, Wd, A.F, col, row, v, lon_n, lat_n, lon_f, lat_f);
     if (A.lonlat_near) {
       A.lonlat_near[2 * k] = lon_n;
       A.lonlat_near[2 * k + 1] = lat_n;
@@ -248,32 +295,6 @@ void rpc_rays_kernel(const bn_rpc R, const World Wd, const RayArgs A) {
       A.lonlat_far[2 * k] = lon_f;
       A.lonlat_far[2 * k + 1] = lat_f;
     }
-    double nx, ny, nz, fx, fy, fz;
-    geo_world(Wd, lon_n, lat_n, A.max_alt, nx, ny, nz);
-    geo_world(Wd, lon_f, lat_f, A.min_alt, fx, fy, fz);
-    const double dx = fx - nx, dy = fy - ny, dz = fz - nz;
-    const double len = sqrt((dx * dx + dy * dy) + dz * dz);
-    float v[8];
-    v[3] = (float)(dx / len);
-    v[4] = (float)(dy / len);
-    v[5] = (float)(dz / len);
-    v[6] = 0.f;
-    if (A.round_f32) {
-      const float rg = (float)A.range;
-      v[0] = ((float)nx - (float)A.cx) / rg;
-      v[1] = ((float)ny - (float)A.cy) / rg;
-      v[2] = ((float)nz - (float)A.cz) / rg;
-      v[7] = (float)len / rg;
-    } else {
-      v[0] = (float)((nx - A.cx) / A.range);
-      v[1] = (float)((ny - A.cy) / A.range);
-      v[2] = (float)((nz - A.cz) / A.range);
-      v[7] = (float)(len / A.range);
-    }
-    bool finite = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) finite = finite && isfinite(v[i]);
-    bad = bad || !finite;
     float *out = A.rays + k * A.ray_stride;
 #pragma unroll
     for (int i = 0; i < 8; ++i) out[i] = bad ? __builtin_nanf("") : v[i];
@@ -284,6 +305,97 @@ void rpc_rays_kernel(const bn_rpc R, const World Wd, const RayArgs A) {
     }
   }
   count_block(bad, A.counts);
+}
+
+// The tie-point depth priors of a view ("The depth priors of a view" in the header).  Two launches, one lane per tie point:
+// tie_owner_kernel settles which tie owns a pixel with an integer atomicMax, tie_priors_kernel runs the ray chain and the
+// prior arithmetic for the owners only and scatters them; distinct pixels have distinct destinations, so no write races.
+__global__ __launch_bounds__(CAM_BLOCK)
+void tie_owner_kernel(const int32_t *__restrict__ px, int32_t T, int32_t H, int32_t W, int32_t *__restrict__ owner,
+                      unsigned long long *__restrict__ counts) {
+  const int64_t t = (int64_t)blockIdx.x * CAM_BLOCK + threadIdx.x;
+  bool outside = false, dup = false;
+  if (t < T) {
+    const int32_t col = px[2 * t], row = px[2 * t + 1];
+    outside = col < 0 || col >= W || row < 0 || row >= H;
+    if (!outside) dup = atomicMax(&owner[(int64_t)row * W + col], (int32_t)t) != -1;
+  }
+  count_block(outside, counts);
+  count_block(dup, counts + 1);
+}
+
+struct TieArgs {
+  const int32_t *px, *owner, *dst_row, *dst_col;
+  const double *pts3d, *correl;
+  int32_t T, H, W, Hout, Wout;
+  double downscale, cmin, cmax, corrscale;
+  float stdscale, margin, std_span;
+  Frame F;
+  float *valid, *depths, *depth_std, *rays, *points, *valid_full, *tie_rays;
+  unsigned long long *counts;
+};
+
+__global__ __launch_bounds__(CAM_BLOCK)
+void tie_priors_kernel(const bn_rpc R, const World Wd, const TieArgs A) {
+  const int64_t t = (int64_t)blockIdx.x * CAM_BLOCK + threadIdx.x;
+  bool skipped = false, unsampled = false;
+  if (t < A.T) {
+    const int32_t col = A.px[2 * t], row = A.px[2 * t + 1];
+    const bool inside = col >= 0 && col < A.W && row >= 0 && row < A.H;
+    const int64_t pix = (int64_t)row * A.W + col;
+    if (inside && A.owner[pix] == (int32_t)t) {
+      float v[8];
+      double lon_n, lat_n, lon_f, lat_f;
+      skipped = ray_chain(R, Wd, A.F, (double)col / A.downscale, (double)row / A.downscale, v, lon_n, lat_n, lon_f, lat_f);
+      if (A.tie_rays) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) A.tie_rays[8 * t + i] = skipped ? __builtin_nanf("") : v[i];
+      }
+      const double X = A.pts3d[3 * t], Y = A.pts3d[3 * t + 1], Z = A.pts3d[3 * t + 2];
+      float p[3];
+      if (A.F.round_f32) {
+        const float rg = (float)A.F.range;
+        p[0] = ((float)X - (float)A.F.cx) / rg;
+        p[1] = ((float)Y - (float)A.F.cy) / rg;
+        p[2] = ((float)Z - (float)A.F.cz) / rg;
+      } else {
+        p[0] = (float)((X - A.F.cx) / A.F.range);
+        p[1] = (float)((Y - A.F.cy) / A.F.range);
+        p[2] = (float)((Z - A.F.cz) / A.F.range);
+      }
+      const float tx = p[0] - v[0], ty = p[1] - v[1], tz = p[2] - v[2];
+      const float depth = sqrtf((tx * tx + ty * ty) + tz * tz);
+      const double cn = ((A.correl[t] - A.cmin) / (A.cmax - A.cmin)) * A.corrscale;
+      const float w = (float)cn * (-v[5]);
+      const float s = A.stdscale * (1.0f - w) + A.margin;
+      skipped = skipped || !(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && isfinite(depth) && isfinite(w) && isfinite(s));
+      if (!skipped) {
+        if (A.points) {
+          A.points[3 * pix] = p[0];
+          A.points[3 * pix + 1] = p[1];
+          A.points[3 * pix + 2] = p[2];
+        }
+        if (A.valid_full) A.valid_full[pix] = 1.f;
+        const int32_t dr = A.dst_row ? A.dst_row[row] : row, dc = A.dst_col ? A.dst_col[col] : col;
+        unsampled = dr < 0 || dr >= A.Hout || dc < 0 || dc >= A.Wout;
+        if (!unsampled) {
+          const int64_t q = (int64_t)dr * A.Wout + dc;
+          A.valid[q] = 1.f;
+          if (A.depths) {
+            A.depths[2 * q] = depth;
+            A.depths[2 * q + 1] = w;
+          }
+          if (A.depth_std) A.depth_std[q] = s * A.std_span;
+          if (A.rays) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) A.rays[8 * q + i] = v[i];
+          }
+        }
+      }
+    }
+  }
+  count_block(skipped, A.counts + 2);
+  count_block(unsampled, A.counts + 3);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
@@ -384,12 +496,62 @@ extern "C" int bn_rpc_rays(const bn_rpc *rpc, const double *cols, const double *
   BN_REQUIRE(rpc_ok(rpc), "rpc_rays: the descriptor has a zero scale or a non-finite entry");
   if (r1 == r0) return 0;
   RayArgs a;
-  a.cols = cols; a.rows = rows; a.W = W; a.round_f32 = round_f32; a.has_sun = sun != nullptr;
+  a.cols = cols; a.rows = rows; a.W = W; a.has_sun = sun != nullptr;
   a.r0 = r0; a.r1 = r1; a.ray_stride = ray_stride;
-  a.min_alt = min_alt; a.max_alt = max_alt; a.cx = center[0]; a.cy = center[1]; a.cz = center[2]; a.range = range;
+  a.F = Frame{round_f32, min_alt, max_alt, center[0], center[1], center[2], range};
   for (int i = 0; i < 3; ++i) a.sun[i] = sun ? sun[i] : 0.f;
   a.rays = rays; a.lonlat_near = lonlat_near; a.lonlat_far = lonlat_far; a.counts = counts;
   rpc_rays_kernel<<<(unsigned)ceil_div64(r1 - r0, CAM_BLOCK), CAM_BLOCK, 0, (hipStream_t)stream>>>(*rpc, make_world(cs, zone, south), a);
   BN_LAUNCH_CHECK("rpc_rays");
+  return 0;
+}
+
+extern "C" int bn_tie_owner(const int32_t *px, int32_t T, int32_t H, int32_t W, int32_t *owner, unsigned long long *counts,
+                            void *stream) {
+  BN_REQUIRE(px && owner && counts, "tie_owner: null argument");
+  BN_REQUIRE(T >= 0 && T <= CAM_MAX_RAYS, "tie_owner: T=%d tie points (0 to 2^30)", T);
+  BN_REQUIRE(H >= 1 && W >= 1, "tie_owner: a view of %d x %d pixels", H, W);
+  BN_REQUIRE((int64_t)H * W <= (int64_t)1 << 31, "tie_owner: %d x %d pixels (H W at most 2^31)", H, W);
+  if (T == 0) return 0;
+  tie_owner_kernel<<<(unsigned)ceil_div64(T, CAM_BLOCK), CAM_BLOCK, 0, (hipStream_t)stream>>>(px, T, H, W, owner, counts);
+  BN_LAUNCH_CHECK("tie_owner");
+  return 0;
+}
+
+extern "C" int bn_tie_priors(const bn_rpc *rpc, const int32_t *px, const int32_t *owner, const double *pts3d, const double *correl,
+                             int32_t T, int32_t H, int32_t W, int32_t Hout, int32_t Wout, const int32_t *dst_row,
+                             const int32_t *dst_col, double downscale, double min_alt, double max_alt, int32_t cs, int32_t zone,
+                             int32_t south, const double *center, double range, int32_t round_f32, double cmin, double cmax,
+                             double corrscale, double stdscale, double margin, double std_span, float *valid, float *depths,
+                             float *depth_std, float *rays, float *points, float *valid_full, float *tie_rays,
+                             unsigned long long *counts, void *stream) {
+  BN_REQUIRE(rpc && px && owner && pts3d && correl && center && valid && counts, "tie_priors: null argument");
+  BN_REQUIRE(T >= 0 && T <= CAM_MAX_RAYS, "tie_priors: T=%d tie points (0 to 2^30)", T);
+  BN_REQUIRE(H >= 1 && W >= 1 && Hout >= 1 && Wout >= 1, "tie_priors: a view of %d x %d pixels, an output of %d x %d", H, W, Hout, Wout);
+  BN_REQUIRE((int64_t)H * W <= (int64_t)1 << 31, "tie_priors: %d x %d pixels (H W at most 2^31)", H, W);
+  BN_REQUIRE((dst_row || Hout == H) && (dst_col || Wout == W),
+             "tie_priors: without dst_row / dst_col the output is the view (%d x %d, not %d x %d)", H, W, Hout, Wout);
+  CAM_REQUIRE_WORLD("tie_priors");
+  BN_REQUIRE(round_f32 == 0 || round_f32 == 1, "tie_priors: round_f32=%d (0 or 1)", round_f32);
+  BN_REQUIRE(std::isfinite(downscale) && downscale >= 1.0, "tie_priors: downscale=%g must be finite and at least 1", downscale);
+  BN_REQUIRE(std::isfinite(min_alt) && std::isfinite(max_alt), "tie_priors: altitudes [%g, %g] must be finite", min_alt, max_alt);
+  BN_REQUIRE(range > 0 && std::isfinite(range), "tie_priors: range=%g must be positive and finite", range);
+  BN_REQUIRE(std::isfinite(center[0]) && std::isfinite(center[1]) && std::isfinite(center[2]), "tie_priors: the centre must be finite");
+  BN_REQUIRE(std::isfinite(cmin) && std::isfinite(cmax) && cmax > cmin, "tie_priors: correlations [%g, %g] (finite, cmax > cmin)", cmin,
+             cmax);
+  BN_REQUIRE(std::isfinite(corrscale) && std::isfinite(stdscale) && std::isfinite(margin) && std::isfinite(std_span),
+             "tie_priors: corrscale=%g, stdscale=%g, margin=%g, std_span=%g must be finite", corrscale, stdscale, margin, std_span);
+  BN_REQUIRE(rpc_ok(rpc), "tie_priors: the descriptor has a zero scale or a non-finite entry");
+  if (T == 0) return 0;
+  TieArgs a;
+  a.px = px; a.owner = owner; a.dst_row = dst_row; a.dst_col = dst_col; a.pts3d = pts3d; a.correl = correl;
+  a.T = T; a.H = H; a.W = W; a.Hout = Hout; a.Wout = Wout;
+  a.downscale = downscale; a.cmin = cmin; a.cmax = cmax; a.corrscale = corrscale;
+  a.stdscale = (float)stdscale; a.margin = (float)margin; a.std_span = (float)std_span;
+  a.F = Frame{round_f32, min_alt, max_alt, center[0], center[1], center[2], range};
+  a.valid = valid; a.depths = depths; a.depth_std = depth_std; a.rays = rays; a.points = points; a.valid_full = valid_full;
+  a.tie_rays = tie_rays; a.counts = counts;
+  tie_priors_kernel<<<(unsigned)ceil_div64(T, CAM_BLOCK), CAM_BLOCK, 0, (hipStream_t)stream>>>(*rpc, make_world(cs, zone, south), a);
+  BN_LAUNCH_CHECK("tie_priors");
   return 0;
 }

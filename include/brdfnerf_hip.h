@@ -768,6 +768,49 @@ int bn_rpc_rays(const bn_rpc *rpc, const double *cols, const double *rows, int32
                 double max_alt, int32_t cs, int32_t zone, int32_t south, const double *center, double range, const float *sun,
                 int32_t round_f32, float *rays, int64_t ray_stride, double *lonlat_near, double *lonlat_far,
                 unsigned long long *counts, void *stream);
+/* The depth priors of a view from its tie points (additive to ABI 7): load_depth_data (datasets/satellite_rgb_dep.py:401-548)
+ * for one view, paired BY PIXEL.  Upstream pairs the k-th tie point with the k-th valid pixel in raster order (:474), which is the
+ * pixel pairing only for a file sorted row-major without repeats; here a tie point belongs to the pixel it names.  One lane per
+ * tie point in both launches; camera.hip is compiled with fp contraction off, every operation below is rounded on its own.
+ *
+ * bn_tie_owner: px int32 [T][2] as (col, row) at FULL resolution; owner int32 [H][W], the CALLER fills it with -1.
+ *   A tie point outside [0, W) x [0, H) is left out and counts[0] (outside) += 1.  Otherwise atomicMax(owner[row W + col], t):
+ *   the HIGHEST index owns the pixel, whatever the order of arrival; a tie point that meets a value other than -1 adds 1 to
+ *   counts[1] (duplicates), so the total is (ties inside) - (distinct pixels).  Integer atomics only, one per counter and block.
+ * bn_tie_priors: for tie point t with owner[row W + col] == t only (every other lane does nothing):
+ *   1. ray      step 5 above (the very device function bn_rpc_rays runs) at pixel (col / downscale, row / downscale), the
+ *               division in float64; rpc is the view's descriptor ALREADY rescaled by the caller.  v[0..7] is the ray row.
+ *   2. point    P = pts3d[t] float64 [3] in world units.  round_f32 = 1 (:456-463): p = ((float)P - (float)center) / (float)range
+ *               per axis, in float32; round_f32 = 0: p = (float)((P - center) / range), formed in float64.
+ *   3. depth    t = p - (v0, v1, v2) in float32 ; depth = sqrtf((t.x t.x + t.y t.y) + t.z t.z)
+ *   4. weight   cn = ((correl[t] - cmin) / (cmax - cmin)) corrscale in float64 (:433-436) ; w = (float)cn * (-v5), the
+ *               product with the nadir (0, 0, -1) of :479-492
+ *   5. std      s = (float)stdscale * (1.0f - w) + (float)margin, left to right in float32 (:498) ; depth_std = s *
+ *               (float)std_span.  std_span is upstream's depth_max - depth_min, the literal 0 of :407-408, 539.
+ *   6. skipped  a tie point whose ray is counted by step 5, or whose p, depth, w or s is not finite, writes nothing but
+ *               tie_rays (NaN) and counts[2] (skipped) += 1: its pixel stays invalid.
+ *   7. placing  points float32 [H][W][3] = p and valid_full float32 [H][W] = 1 at the tie point's own pixel (both nullable; the
+ *               input of the normals).  The output pixel is (dst_row[row], dst_col[col]): int32 vectors of H and W entries
+ *               from the host, -1 where the resize samples no such line; NULL is the identity (then Hout == H, Wout == W).
+ *               A tie point whose line is not sampled (or whose entry is outside the output) adds 1 to counts[3] (unsampled);
+ *               otherwise valid float32 [Hout][Wout] = 1, depths float32 [Hout][Wout][2] = (depth, w), depth_std [Hout][Wout],
+ *               rays float32 [Hout][Wout][8] = v (upstream's all_deprays).  No float index arithmetic runs on the device.
+ *   All outputs but valid are nullable, and the CALLER zero-fills them.  tie_rays float32 [T][8] (nullable): v of every owner
+ *   tie point (NaN where its ray is counted); rows of the other tie points are not written.
+ *   counts: int64 [4] = (outside, duplicates, skipped, unsampled), the CALLER zeroes; bn_tie_owner adds to [0] and [1],
+ *   bn_tie_priors to [2] and [3].
+ * Refused (BN_EINVAL): NULL rpc, px, owner, pts3d, correl, center, valid or counts; T < 0 or over 2^30; H, W, Hout or Wout < 1;
+ * H W over 2^31; Hout != H without dst_row, Wout != W without dst_col; a downscale that is not finite or below 1; a cmin, cmax,
+ * corrscale, stdscale, margin or std_span that is not finite; cmax <= cmin; another cs, zone outside [1, 60], south or
+ * round_f32 other than 0 or 1; a range that is not positive and finite; a centre or altitude that is not finite; a scale of
+ * zero (or a non-finite entry) in the descriptor.  T == 0 launches nothing. */
+int bn_tie_owner(const int32_t *px, int32_t T, int32_t H, int32_t W, int32_t *owner, unsigned long long *counts, void *stream);
+int bn_tie_priors(const bn_rpc *rpc, const int32_t *px, const int32_t *owner, const double *pts3d, const double *correl, int32_t T,
+                  int32_t H, int32_t W, int32_t Hout, int32_t Wout, const int32_t *dst_row, const int32_t *dst_col,
+                  double downscale, double min_alt, double max_alt, int32_t cs, int32_t zone, int32_t south, const double *center,
+                  double range, int32_t round_f32, double cmin, double cmax, double corrscale, double stdscale, double margin,
+                  double std_span, float *valid, float *depths, float *depth_std, float *rays, float *points, float *valid_full,
+                  float *tie_rays, unsigned long long *counts, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
