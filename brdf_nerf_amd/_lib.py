@@ -160,6 +160,8 @@ _SIGS = {
     "bn_ray_shade_loss": (C.c_int, [fptr, fptr, fptr, fptr, fptr, fptr, C.c_int64, fptr, C.c_int64, fptr, fptr, C.c_int64, fptr,
                                     C.c_int64, fptr, C.c_int64, fptr, C.c_int64, C.c_int64, fptr, fptr, fptr, C.c_int32, fptr, fptr,
                                     fptr, fptr, fptr, fptr]),
+    "bn_normal_target_loss": (C.c_int, [fptr, C.c_int32, C.c_int32, fptr, C.c_int64, fptr, C.c_int64, fptr, C.c_int64, C.c_float,
+                                        C.c_int64, fptr, fptr, fptr, C.c_int32, fptr, fptr, fptr]),
     "bn_ray_shade_dirs": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int64, fptr, fptr, C.c_int64, C.c_int32, fptr, fptr, fptr]),
     "bn_sample_shade_dirs": (C.c_int, [fptr, fptr, fptr, fptr, C.c_int64, fptr, fptr, C.c_int64, C.c_int32, C.c_int32, fptr, C.c_int64,
                                        fptr, C.c_int64, fptr]),

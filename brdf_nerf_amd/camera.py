@@ -481,7 +481,7 @@ def depth_priors(rpc, H, W, pts2d, pts3d, correl, min_alt, max_alt, center, rang
 
 @torch.no_grad()
 def ray_table(views, images, center, range=None, cs="utm", zone=None, south=False, precision="reference", device=None, seed=0,
-              chunk=None, priors=None, corrscale=1.0, stdscale=1.0, margin=1e-4, std_span=0.0):
+              chunk=None, priors=None, corrscale=1.0, stdscale=1.0, margin=1e-4, std_span=0.0, want_normals=False):
     """The views of a scene as one RayTable (load_data, :311-394, and with `priors` load_depth_data, :401-548: the whole of
     load_train_split without the file readers): views as scene_bounds takes them, each with "sun": (elevation_deg, azimuth_deg);
     images: per view the (H W, 3) colours, row-major.  cs='utm' without a zone: the zone of the first view's lat / lon offset.
@@ -489,13 +489,18 @@ def ray_table(views, images, center, range=None, cs="utm", zone=None, south=Fals
     1e-4 - and std_span are its parameters): the table gains depths, valid_depth and depth_std, a view with None has
     valid_depth = 0 rows.  A view's "H", "W" are its ray grid - the image AFTER its "downscale"; the tie points of a downscaled
     view are at full resolution, which the view names as "full_H", "full_W" (their resize must be H x W).  priors=None: the
-    table without depth columns."""
+    table without depth columns.  want_normals (with priors): the table also gains depth_priors' normals and valid_normal - what
+    FusedTrainer's nr_spv_type 2 / 3 read; a view with None has the normal (0, 0, 1) and valid_normal = 0."""
     from .raytable import RayTable
     if len(views) != len(images) or not views:
         raise ValueError(f"ray_table: {len(views)} views and {len(images)} images")
     if priors is not None and len(priors) != len(views):
         raise ValueError(f"ray_table: {len(views)} views and {len(priors)} priors")
     tables, cols = [], {"depths": [], "valid_depth": [], "depth_std": []}
+    if want_normals:
+        if priors is None:
+            raise ValueError("ray_table: want_normals needs priors (the normals come from the tie points)")
+        cols.update(normals=[], valid_normal=[])
     for i, (v, img) in enumerate(zip(views, images)):
         rpc, H, W, min_alt, max_alt = _view_args(v)
         if cs == "utm" and zone is None:
@@ -510,6 +515,9 @@ def ray_table(views, images, center, range=None, cs="utm", zone=None, south=Fals
         if priors[i] is None:
             pr = {"depths": torch.zeros((H * W, 2), device=rays.device), "valid_depth": torch.zeros((H * W,), device=rays.device),
                   "depth_std": torch.zeros((H * W,), device=rays.device)}
+            if want_normals:
+                pr["normals"] = torch.tensor([0.0, 0.0, 1.0], device=rays.device).repeat(H * W, 1)
+                pr["valid_normal"] = torch.zeros((H * W,), device=rays.device)
         else:
             missing = [k for k in ("pts2d", "pts3d", "correl") if k not in priors[i]]
             if missing:
@@ -520,11 +528,11 @@ def ray_table(views, images, center, range=None, cs="utm", zone=None, south=Fals
             pr = depth_priors(rpc, int(v.get("full_H", H)), int(v.get("full_W", W)), priors[i]["pts2d"], priors[i]["pts3d"],
                               priors[i]["correl"], min_alt, max_alt, center, range, cs=cs, zone=zone, south=south, downscale=down,
                               corrscale=corrscale, stdscale=stdscale, margin=margin, std_span=std_span, precision=precision,
-                              want_normals=False, device=rays.device)
+                              want_normals=bool(want_normals), device=rays.device)
             if pr["shape"] != (H, W):
                 raise ValueError(f"ray_table: the priors of view {i} come out {pr['shape'][0]} x {pr['shape'][1]}, its rays are {H} x {W}")
         for k in cols:
-            cols[k].append(pr[k])
+            cols[k].append(pr[k].float())
     rays = torch.cat(tables, 0)
     rgbs = torch.cat([torch.as_tensor(img).to(rays.device).float() for img in images], 0)
     if priors is None:

@@ -683,6 +683,29 @@ def ray_shade_loss(desc, acc, wsum, depth, var, rays_d, sun_d, rgbs, bufs=None, 
     return o
 
 
+def normal_target_loss(acc, ch, normals, valid_normal, valid_depth, lambda_nr_spv, d_acc, ray_loss=None, loss_acc=None,
+                       nonfinite=None, count=None):
+    """NormalLoss 'an' / 'lr' (metrics.py:218-261, --nr_spv_type 3 / 2) on the composited normal acc[:, ch:ch+3] against the rays'
+    target normals (bn_normal_target_loss): ADDS its gradient into d_acc[:, ch:ch+3] and its per-ray terms into ray_loss /
+    loss_acc.  acc, d_acc (R,C) contiguous; normals (R,3) view with unit inner stride; valid_normal, valid_depth (R,) views (any
+    stride >= 0).  nonfinite (int64[2]): rays whose term is not finite are left out and counted.  count: int64[1] scratch for the
+    number of selected rays (allocated when None).  -> count."""
+    R, Cc = acc.shape
+    for t in (acc, d_acc):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (R, Cc)
+    np_, ns = _rows3(normals, R)
+    vnp, vns = _strided(valid_normal)
+    vdp, vds = _strided(valid_depth)
+    assert valid_normal.shape[0] == R and valid_depth.shape[0] == R
+    if count is None:
+        count = torch.empty(1, dtype=torch.int64, device=acc.device)
+    assert count.is_cuda and count.dtype == torch.int64 and count.numel() >= 1
+    L.check(L.lib().bn_normal_target_loss(_p(acc), Cc, int(ch), np_, ns, vnp, vns, vdp, vds, float(lambda_nr_spv), R, _p(d_acc),
+                                          _p(ray_loss), _p(loss_acc), 0 if loss_acc is None else loss_acc.numel(), _p(nonfinite),
+                                          _p(count), _stream()), "bn_normal_target_loss")
+    return count
+
+
 def ray_shade_dirs(desc, acc, wsum, rays_d, sun, view=None, rgb=None, brdf=None, want_brdf=False):
     """The shading of ray_shade_loss under K directions in one launch (bn_ray_shade_dirs), forward only.  acc (R,C), wsum (R,);
     rays_d (R,3) view with unit inner stride; sun (K,3); view (K,3) or None (-rays_d).  -> rgb (K,R,3) and brdf (K,R,3) or None

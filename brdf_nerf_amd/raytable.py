@@ -1,7 +1,8 @@
 """On-device ray table and batch sampler (replaces DataLoader(shuffle=True, num_workers=4), main.py:170-184).
 
 The training set of the reference is one concatenated table of rows `[o3, d3, near, far, sun3]` with rgb (N,3) and,
-for the depth-supervised variants, depths (N,2), valid_depth (N), depth_std (N) (satellite_rgb_dep.py:311-394, 708-716).
+for the depth-supervised variants, depths (N,2), valid_depth (N), depth_std (N) (satellite_rgb_dep.py:311-394, 708-716) and,
+for the normal supervision of --nr_spv_type 2 / 3, the tie-point normals (N,3) with valid_normal (N) (:511-514).
 Here the table stays in HBM and a batch is a gather by a slice of a per-epoch permutation drawn on the device: no
 worker processes, no pinned-memory copies, no host sync.  Under data parallelism every rank draws the same permutation
 (same seed) and takes its own contiguous share of each global batch (distributed.shard_bounds).
@@ -12,15 +13,17 @@ import torch
 
 from .distributed import shard_bounds
 
-_KEYS = ("rays", "rgbs", "depths", "valid_depth", "depth_std")
+_KEYS = ("rays", "rgbs", "depths", "valid_depth", "depth_std", "normals", "valid_normal")
 
 
 class RayTable:
-    def __init__(self, rays, rgbs, depths=None, valid_depth=None, depth_std=None, device=None, seed=0):
+    def __init__(self, rays, rgbs, depths=None, valid_depth=None, depth_std=None, device=None, seed=0, normals=None,
+                 valid_normal=None):
         dev = torch.device(device) if device is not None else rays.device
         n = rays.shape[0]
         self.data = {"rays": rays.to(dev).float().contiguous(), "rgbs": rgbs.to(dev).float().contiguous()}
-        for k, v in (("depths", depths), ("valid_depth", valid_depth), ("depth_std", depth_std)):
+        for k, v in (("depths", depths), ("valid_depth", valid_depth), ("depth_std", depth_std), ("normals", normals),
+                     ("valid_normal", valid_normal)):
             if v is not None:
                 assert v.shape[0] == n, k
                 self.data[k] = v.to(dev).float().contiguous()
@@ -74,9 +77,10 @@ class RayTable:
         self.cursor, self.epoch = int(sd["cursor"]), int(sd["epoch"])
 
 
-def synthetic_table(n_rays, n_images=3, device="cpu", seed=1, with_depth=True):
+def synthetic_table(n_rays, n_images=3, device="cpu", seed=1, with_depth=True, with_normals=False):
     """Djibouti-shaped synthetic table: normalised scene cube, near-nadir views, one sun direction
-    per image, near = 0, far constant per image."""
+    per image, near = 0, far constant per image.  with_normals (needs with_depth): near-vertical unit target normals and a
+    valid_normal flag that is independent of valid_depth, drawn after everything else (the other columns stay what they were)."""
     g = torch.Generator().manual_seed(seed)
     per = (n_rays + n_images - 1) // n_images
     rows = []
@@ -96,5 +100,10 @@ def synthetic_table(n_rays, n_images=3, device="cpu", seed=1, with_depth=True):
     if with_depth:
         kw = dict(depths=torch.stack([0.8 + 0.4 * torch.rand(n_rays, generator=g), torch.rand(n_rays, generator=g)], -1),
                   valid_depth=(torch.rand(n_rays, generator=g) < 0.7).float(), depth_std=torch.zeros(n_rays))
+    if with_normals:
+        if not with_depth:
+            raise ValueError("synthetic_table: with_normals needs with_depth (the normal term selects rays by valid_depth)")
+        n = torch.cat([0.3 * torch.randn(n_rays, 2, generator=g), torch.ones(n_rays, 1)], -1)
+        kw.update(normals=n / n.norm(dim=-1, keepdim=True), valid_normal=(torch.rand(n_rays, generator=g) < 0.8).float())
     return RayTable(rays, rgbs, device=device, seed=seed, **kw)
 

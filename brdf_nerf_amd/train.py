@@ -44,10 +44,21 @@ class TrainLoop:
             if self.embedding_t is not None:                # main.py:116-117
                 load_ckpt(self.embedding_t, in_ckpts, model_name="embedding_t", trusted=trusted_ckpts)
         g = lambda k, d=0.0: getattr(args, k, d)
+        # --nr_spv_type 0 is resolved from --normal (opt.py:328-334); a model without a normal field keeps 0: no supervision
+        spv_type = int(g("nr_spv_type", 1))
+        if spv_type == 0:
+            spv_type = {"analystic_learned": 1, "learned": 2, "analystic": 3}.get(getattr(args, "normal", "none"), 0)
+        if spv_type in (2, 3) and abs(g("nr_spv_lambda")) > 1e-5:
+            missing = [k for k in ("normals", "valid_normal", "valid_depth") if k not in table.data]
+            if missing:
+                raise ValueError(f"--nr_spv_type {spv_type} with --nr_spv_lambda {g('nr_spv_lambda')} supervises the field's normal by "
+                                 f"the tie-point normals, but the ray table has no column {', '.join(repr(k) for k in missing)}: "
+                                 f"build it with camera.ray_table(priors=..., want_normals=True)")
         self.trainer = FusedTrainer(self.model, args, lr=args.lr, lambda_rgb=g("lambda_rgb", 1.0), ds_lambda=g("ds_lambda"),
                                     usealldepth=bool(g("usealldepth", False)), process_group=process_group, strict_rng=False,
                                     nr_reg_an_lambda=g("nr_reg_an_lambda"), nr_reg_lr_lambda=g("nr_reg_lr_lambda"),
-                                    hs_lambda=g("hs_lambda"), nr_spv_lambda=g("nr_spv_lambda") if g("nr_spv_type", 1) == 1 else 0.0)
+                                    hs_lambda=g("hs_lambda"), nr_spv_lambda=g("nr_spv_lambda") if spv_type else 0.0,
+                                    nr_spv_type=spv_type)
         self.schedule = StageSchedule(args, len(table), self.world)
         self._lambda_rgb = float(g("lambda_rgb", 1.0))
         self._trusted_ckpts = bool(trusted_ckpts)
@@ -89,7 +100,7 @@ class TrainLoop:
             loss, rgb = tr.step(b["rays"], b["rgbs"], valid_depth=b.get("valid_depth"), depths=depths,
                                 depth_std=b.get("depth_std"), apply_brdf=flags["apply_brdf"], apply_theta=flags["apply_theta"],
                                 cos_irra_on=flags["cos_irra_on"], depth_loss_on=flags["depth_loss_on"], near_far=self.near_far,
-                                gsam_only=flags["gsam_only"])
+                                gsam_only=flags["gsam_only"], normals=b.get("normals"), valid_normal=b.get("valid_normal"))
         finally:
             tr.reg = saved
         sch.end_step()

@@ -50,21 +50,34 @@ class _Rows:
         return a[block.row0:block.row0 + block.out.shape[0]]
 
 
-def _reg_lambdas(spec, reg):
+def _reg_lambdas(spec, reg, spv_type=1):
     """(hs, nr_an, nr_lr, nr_spv) of a step's regularisers as the kernels take them; NormalLoss (nr_spv_type 1, main.py:297-303)
-    compares the two normal fields, so it is off unless the spec has both."""
-    spv = float(reg.get("nr_spv", 0)) if (spec.normal_an and spec.normal_lr and abs(reg.get("nr_spv", 0)) > 1e-5) else 0.0
+    compares the two normal fields, so it is off unless the spec has both (types 2 / 3: _target_normal, not this entry)."""
+    spv = float(reg.get("nr_spv", 0)) if (spv_type == 1 and spec.normal_an and spec.normal_lr and abs(reg.get("nr_spv", 0)) > 1e-5) else 0.0
     return float(reg.get("hs", 0)), float(reg.get("nr_an", 0)), float(reg.get("nr_lr", 0)), spv
 
 
 class FusedTrainer:
     def __init__(self, model, args, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, lambda_rgb=1.0, ds_lambda=0.0,
                  usealldepth=False, process_group=None, strict_rng=True, reuse_coarse=True, nr_reg_an_lambda=0.0,
-                 nr_reg_lr_lambda=0.0, hs_lambda=0.0, nr_spv_lambda=0.0, data_parallel=True):
+                 nr_reg_lr_lambda=0.0, hs_lambda=0.0, nr_spv_lambda=0.0, data_parallel=True, nr_spv_type=1):
         """The regulariser lambdas are the reference's --nr_reg_an_lambda / --nr_reg_lr_lambda / --hs_lambda /
         --nr_spv_lambda (opt.py:232-246, all 0 by default); WHEN they act (train_steps > nrrg_on, epoch > 2, main.py:271-327)
-        is the caller's schedule: pass regularisers=False to step() until then."""
+        is the caller's schedule: pass regularisers=False to step() until then.
+        nr_spv_type: the RESOLVED --nr_spv_type (opt.py:328-334 turns 0 into 1 / 2 / 3 by --normal; TrainLoop does the same).  1: NormalLoss
+        between the two normal fields.  3: the composited analytic normal against the tie-point normals of the rays with a depth prior
+        (main.py:316-320, keyword 'an'), 2: the same rule on the learned normal - upstream's type 2 raises a NameError
+        (metrics.py:235: target_valid_depth is not passed), so that is this project's reading of it.  Types 2 and 3 need step()'s
+        normals / valid_normal / valid_depth; with a non-zero lambda, a type whose normal field the model lacks is a ValueError here
+        (upstream prints and goes on)."""
         self.model, self.args = model, args
+        self.nr_spv_type = int(nr_spv_type)
+        if self.nr_spv_type not in (0, 1, 2, 3):
+            raise ValueError(f"nr_spv_type={nr_spv_type}: expected 1, 2 or 3 (0: no normal supervision)")
+        field = {2: ("learned", ("analystic_learned", "learned")), 3: ("analytic", ("analystic_learned", "analystic"))}.get(self.nr_spv_type)
+        if field is not None and abs(nr_spv_lambda) > 1e-5 and model.normal not in field[1]:
+            raise ValueError(f"nr_spv_type={self.nr_spv_type} supervises the {field[0]} normal, which a model with "
+                             f"normal={model.normal!r} does not have")
         self.reg = dict(nr_an=nr_reg_an_lambda, nr_lr=nr_reg_lr_lambda, hs=hs_lambda, nr_spv=nr_spv_lambda)
         self.fused_glue = True      # Lambertian steps: one launch for shading + losses + their gradients
         # The BRDF models have genuine singularities (Hapke's azimuth phi = acos(.) at phi -> 0, grazing angles): autograd -
@@ -198,9 +211,13 @@ class FusedTrainer:
 
     # ------------------------------------------------------------------ one step
     def step(self, rays, rgbs, valid_depth=None, depths=None, depth_std=None, apply_brdf=False, apply_theta=False,
-             cos_irra_on=False, depth_loss_on=True, near_far=None, regularisers=True, gsam_only=False):
+             cos_irra_on=False, depth_loss_on=True, near_far=None, regularisers=True, gsam_only=False, normals=None,
+             valid_normal=None):
         """gsam_only (main.py:201-203, rendering.py:266-269): pass 1 only guides the sampling; the step renders, and
-        back-propagates through, the G guided samples alone."""
+        back-propagates through, the G guided samples alone.
+        normals (R,3), valid_normal (R,): the tie-point normals of the rays and their validity (camera.depth_priors), read by
+        nr_spv_type 2 / 3 on the rays with valid_depth > 0 - whatever depth_loss_on says (upstream adds the term in every depth
+        stage); the term is off when |nr_spv_lambda| <= 1e-5 or one of normals, valid_normal, valid_depth is None."""
         model, args = self.model, self.args
         S, G = args.n_samples, args.guided_samples
         R = rays.shape[0]
@@ -218,7 +235,7 @@ class FusedTrainer:
                 and (not sun_on or sun_lean)
                 and rays.dtype == torch.float32 and rays.is_contiguous() and rays.shape[1] >= 8 and S + G <= 512):
             return self._step_lean(spec, rays, rgbs, valid_depth, depths, depth_std, apply_brdf, apply_theta, cos_irra_on,
-                                   depth_loss_on, near_far, regularisers, gsam_only)
+                                   depth_loss_on, near_far, regularisers, gsam_only, normals, valid_normal)
         self._grads_clean = False
         named = model.named()
         packed = model.repack(spec)
@@ -335,8 +352,13 @@ class FusedTrainer:
                 loss = loss + losses.normal_reg_loss(normal_leaf("normal_lr"), weights_l, -rays_d, reg["nr_lr"])[0]
             if reg.get("hs", 0) > 0:
                 loss = loss + losses.hard_surface_loss(z_all, depth_l, weights_l, reg["hs"])
-            if abs(reg.get("nr_spv", 0)) > 1e-5 and spec.normal_an and spec.normal_lr:   # nr_spv_type 1 (main.py:297-303)
+            if self.nr_spv_type == 1 and abs(reg.get("nr_spv", 0)) > 1e-5 and spec.normal_an and spec.normal_lr:   # (main.py:297-303)
                 loss = loss + losses.normal_loss(weights_l, normal_leaf("normal_an"), normal_leaf("normal_lr"), reg["nr_spv"])
+            nt = self._target_normal(spec, reg, normals, valid_normal, valid_depth)
+            if nt is not None:                                                         # nr_spv_type 2 / 3 (main.py:310-322)
+                kw = "an" if self.nr_spv_type == 3 else "lr"
+                loss = loss + losses.normal_loss(weights_l, normals.float(), normal_leaf("normal_" + kw), nt[1], keyword=kw,
+                                                 target_weight=valid_normal.float(), valid_depth=valid_depth)
             leaves = [acc_l, depth_l, weights_l] + list(n_leaf.values()) + ([out3_l] if per_sample else [])
             grads = torch.autograd.grad(loss, leaves, allow_unused=True)
             d_acc, d_depth, d_weights = grads[:3]
@@ -384,6 +406,16 @@ class FusedTrainer:
             t = self._nf_dev[key] = torch.tensor(key, dtype=torch.float32, device=rays.device)
         return t
 
+    def _target_normal(self, spec, reg, normals, valid_normal, valid_depth):
+        """(channel of the supervised normal, lambda) of NormalLoss against the rays' target normals (nr_spv_type 2 / 3), or None when
+        the term is off: |lambda| <= 1e-5 (main.py:302) or a missing column.  It does not depend on the depth stage."""
+        lam = float(reg.get("nr_spv", 0))
+        if self.nr_spv_type not in (2, 3) or abs(lam) <= 1e-5 or normals is None or valid_normal is None or valid_depth is None:
+            return None
+        if not (spec.normal_an if self.nr_spv_type == 3 else spec.normal_lr):
+            return None
+        return (spec.ch_normal_an if self.nr_spv_type == 3 else spec.ch_normal_lr), lam
+
     def _active_groups(self, apply_brdf, apply_theta):
         """Which Adam groups (in the order of self.groups) are in this step's graph: torch.optim.Adam would see grad None for the
         others and skip them."""
@@ -418,7 +450,7 @@ class FusedTrainer:
         return float(np.float32(self.args.noise_std))
 
     def _step_lean(self, spec, rays, rgbs, valid_depth, depths, depth_std, apply_brdf, apply_theta, cos_irra_on, depth_loss_on,
-                   near_far, regularisers, gsam_only=False):
+                   near_far, regularisers, gsam_only=False, normals=None, valid_normal=None):
         reg = self.reg if regularisers else {}
         if not self._grads_clean:          # the general path leaves its gradient in the flat buffer
             self.flat_grad.zero_()
@@ -438,17 +470,21 @@ class FusedTrainer:
         use_ds = self.ds_lambda > 0 and depth_loss_on and valid_depth is not None
         valid_depth, depths = stage("valid_depth", valid_depth), stage("depths", depths)
         depth_std = stage("depth_std", depth_std, flat=True)
+        # NormalLoss against the rays' target normals (nr_spv_type 2 / 3): its two columns are staged like the depth columns
+        nt = self._target_normal(spec, reg, normals, valid_normal, valid_depth)
+        if nt is not None:
+            nt = nt + (stage("normals", normals), stage("valid_normal", valid_normal, flat=True))
         nf = self._near_far(rays, near_far)
         active = self._active_groups(apply_brdf, apply_theta)
         self._sync_state()
         slot = self._rng_step % 64
         body = lambda: self._lean_body(spec, rays, rgbs, valid_depth, depths, depth_std, apply_brdf, cos_irra_on, use_ds, nf, reg,
-                                       active, gsam_only)
+                                       active, gsam_only, nt)
         if self.use_graph and self.world == 1 and self.seed_hook is None:
             sig = self._graph_signature(spec, rays, rgbs, valid_depth, depths, depth_std, nf, use_ds, active, apply_brdf, cos_irra_on,
-                                        reg, gsam_only)
+                                        reg, gsam_only, nt)
             # the inputs stay alive with a captured step: their addresses are baked into it
-            loss, rgb = self._replay_or_capture(sig, body, [rays, rgbs, valid_depth, depths, depth_std, nf])
+            loss, rgb = self._replay_or_capture(sig, body, [rays, rgbs, valid_depth, depths, depth_std, nf] + list((nt or ())[2:]))
         else:
             loss, rgb = body()
         self._grads_clean = not self.keep_grads
@@ -462,10 +498,12 @@ class FusedTrainer:
         return loss.detach(), rgb.detach()
 
     def _graph_signature(self, spec, rays, rgbs, valid_depth, depths, depth_std, nf, use_ds, active, apply_brdf, cos_irra_on, reg,
-                         gsam_only):
-        """Everything a captured step bakes in: two steps with equal signatures issue the same launches with the same arguments."""
+                         gsam_only, nt=None):
+        """Everything a captured step bakes in: two steps with equal signatures issue the same launches with the same arguments.
+        nt: the target-normal term of _step_lean (type, channel and the addresses of its two staged columns; its lambda is reg's)."""
         model, args = self.model, self.args
-        return (spec.key(), rays.shape, rays.data_ptr(), rgbs.data_ptr(), None if valid_depth is None else valid_depth.data_ptr(),
+        return (None if nt is None else (int(self.nr_spv_type), int(nt[0]), nt[2].data_ptr(), nt[3].data_ptr()),
+                spec.key(), rays.shape, rays.data_ptr(), rgbs.data_ptr(), None if valid_depth is None else valid_depth.data_ptr(),
                 None if depths is None else depths.data_ptr(), None if depth_std is None else depth_std.data_ptr(),
                 nf.data_ptr(), use_ds, tuple(active), float(self.ds_lambda), float(self.lambda_rgb), bool(self.usealldepth),
                 L.deterministic(), int(self.ray_offset), bool(self.keep_grads), bool(self.merge_passes), bool(apply_brdf),
@@ -521,7 +559,7 @@ class FusedTrainer:
         return out
 
     def _lean_body(self, spec, rays, rgbs, valid_depth, depths, depth_std, apply_brdf, cos_irra_on, use_ds, nf, reg, active,
-                   gsam_only=False):
+                   gsam_only=False, nt=None):
         model, args = self.model, self.args
         S, G = args.n_samples, args.guided_samples
         R, C = rays.shape[0], spec.out_channels
@@ -601,10 +639,12 @@ class FusedTrainer:
                     blocks = [_Block(out1, stash1, z, None, S, 0, 0), _Block(out2, stash2, z2, None, G, 0, R * S)]
                 rows = _Rows(blocks, z_all, idx, (out1.view(R, S, C), out2.view(R, G, C)), self._buf("d_all", (n_all, C)))
             # the rest of the step reads `rows` alone: which arrays hold the samples is decided above and nowhere else
-            hs, nr_an, nr_lr, spv = regs = _reg_lambdas(spec, reg)
+            hs, nr_an, nr_lr, spv = regs = _reg_lambdas(spec, reg, self.nr_spv_type)
             lambda_ds = self.ds_lambda if use_ds else 0.0
             targets = (valid_depth, depths[:, 0], depths[:, 1], depth_std) if use_ds else (None, None, None, None)
-            tail = functools.partial(self._ray_tail, spec, rows, rays, rgbs, targets, lambda_ds, nz2)
+            # (the target-normal term reads valid_depth whether DepthLoss is on or not)
+            ntarget = None if nt is None else nt + (valid_depth,)
+            tail = functools.partial(self._ray_tail, spec, rows, rays, rgbs, targets, lambda_ds, nz2, ntarget=ntarget)
             kdesc = shade_desc(model, args, spec, apply_brdf, cos_irra_on)       # (built per eager step: its inputs may change on a live trainer)
             multi = bool(model.MultiBRDF) and apply_brdf
             sun_rows = sun_on and (multi or kdesc.kind == L.BN_SHADE_LAMBERT)
@@ -620,7 +660,8 @@ class FusedTrainer:
                 sun_col = 8 if args.data == "sat" else -1
                 # no regulariser: a 4-channel copy [bp, sigma] for the one-launch Lambertian tail; with one: a FULL-width copy for the
                 # generic compositing kernels, which carry NormalRegLoss / NormalLoss / HardSurfaceLoss on the per-sample normals and weights
-                with_reg = hs > 0 or spv != 0.0 or nr_an > 0 or nr_lr > 0
+                # (the target-normal term reads the composited normal: a regulariser in this sense)
+                with_reg = hs > 0 or spv != 0.0 or nr_an > 0 or nr_lr > 0 or nt is not None
                 Bd = self._buf("B_full" if with_reg else "B_4", (rows.n, C if with_reg else 4))
                 d_B = self._buf("d_Bfull" if with_reg else "d_B", Bd.shape)
                 for b in rows.blocks:
@@ -673,13 +714,16 @@ class FusedTrainer:
                           active, st, self.betas, self.eps, self.wd, 1.0 / self.world, zero_grad=not keep)
         return loss, rgb
 
-    def _ray_tail(self, spec, rows, rays, rgbs, targets, lambda_ds, noise, src, grads, pad=None, desc=None, regs=None, sun_d=None):
+    def _ray_tail(self, spec, rows, rays, rgbs, targets, lambda_ds, noise, src, grads, pad=None, desc=None, regs=None, sun_d=None,
+                  ntarget=None):
         """Everything between the field forward and the field backward that works on whole rays: compositing of the depth-sorted
         row set read through `src` (its (R, S1, c) / (R, S2, c) views), shading, the losses and the backward of all of it into the
         views `grads`.  `pad` (a Lambertian rgb with this padding): ONE launch (bn_lambert_tail).  `desc` + `regs` (a bn_shade_desc,
         the _reg_lambdas): three - composited sums, the ray-level shading + losses with their gradients w.r.t. those sums
         (bn_ray_shade_loss), the composite backward - plus the one-workgroup reduce of NormalLoss.
-        targets: DepthLoss's (valid, depth, weight, std) or Nones.  -> (loss or None: it is in the step state's loss ring, rgb)."""
+        targets: DepthLoss's (valid, depth, weight, std) or Nones.  ntarget: (channel, lambda, normals, valid_normal, valid_depth) of
+        NormalLoss against the rays' target normals (nr_spv_type 2 / 3; `desc` form only): one entry, two small launches, that adds to
+        the shading's d_acc and to the loss (bn_normal_target_loss).  -> (loss or None: it is in the step state's loss ring, rgb)."""
         R, C = rays.shape[0], spec.out_channels
         z_all, idx = rows.z_all, rows.idx
         # the reported loss: a fixed-order sum of the per-ray terms (repeatable_loss), or atomics into the step state's partials
@@ -688,6 +732,7 @@ class FusedTrainer:
         nonfinite = self._nonfinite if self.sanitize_grads else None
         if desc is None:
             rgb = self._buf("rgb", (R, 3))
+            assert ntarget is None, "the target-normal term needs the generic tail"
             Fn.lambert_tail(z_all, idx, *src, rgbs, pad, self.lambda_rgb, *grads, *targets, lambda_ds, self.usealldepth,
                             ray_loss=ray_loss, loss_acc=loss_acc, rgb=rgb, nonfinite=nonfinite, noise=noise)
         else:
@@ -708,6 +753,10 @@ class FusedTrainer:
             rgb = g["rgb"]
             if spv:
                 Fn.normal_spv_reduce(nreg, R, z_all.shape[1], ray_loss=ray_loss, loss_acc=loss_acc)
+            if ntarget is not None:
+                ch, lam, normals, valid_normal, valid_depth = ntarget
+                Fn.normal_target_loss(o["acc"], ch, normals, valid_normal, valid_depth, lam, g["d_acc"], ray_loss=ray_loss,
+                                      loss_acc=loss_acc, nonfinite=nonfinite, count=self._buf("nt_count", (1,), torch.int64))
             Fn.merged_composite_backward(z_all, idx, *src, None, g["d_depth"], g["d_acc"], *grads, d_wsum=g["d_wsum"],
                                          nonfinite=nonfinite, hs_scale=hs / R if hs > 0 else 0.0, depth=o["depth"], nreg=nreg, noise=noise)
         return (ray_loss.sum() if self.repeatable_loss else None), rgb

@@ -434,6 +434,34 @@ int bn_ray_shade_loss(const bn_shade_desc *desc, const float *acc, const float *
                       const float *target_weight, int64_t tw_stride, const float *target_std, int64_t ts_stride, int64_t R,
                       float *rgb, float *ray_loss, float *loss_acc, int32_t loss_slots, float *d_acc, float *d_wsum,
                       float *d_depth, unsigned long long *nonfinite, const float *extra_loss, void *stream);
+/* NormalLoss against per-ray target normals (additive to ABI 7): metrics.py:218-261 with keyword 'an' (--nr_spv_type 3, main.py:316-320)
+ * or 'lr' (type 2, main.py:310-313), between bn_ray_shade_loss and bn_merged_composite_backward.  It ADDS into the three columns
+ * d_acc[:, ch : ch + 3] that bn_ray_shade_loss wrote and into the step's loss; every other column and every unselected row of d_acc
+ * is left as it is.  acc, d_acc [R][C]; ch the first channel of the composited normal; normals [R] rows of 3 floats, row stride
+ * n_stride elements; valid_normal, valid_depth [R] with element strides (a column of wider storage).
+ * In float32, every operation rounded on its own (no fused multiply-add):
+ *   n_sel = #{r : valid_depth[r] > 0}                 (a NaN does not count; valid_normal plays no part in the count: upstream selects
+ *                                                      by valid_depth and weights by valid_normal, main.py:319, metrics.py:238-242, so
+ *                                                      a selected ray with valid_normal == 0 contributes 0 and still counts)
+ *   n_sel == 0: nothing is added anywhere             (upstream's L1Loss over an empty selection is NaN)
+ *   k = lambda / (3.f * (float)n_sel)
+ *   for a ray r with valid_depth[r] > 0, vn = valid_normal[r]:
+ *     e_c  = vn * normals[r][c] - vn * acc[r][ch + c]                  c = 0, 1, 2: two products, one subtraction
+ *     term = k * ((|e_0| + |e_1|) + |e_2|)
+ *     d_acc[r][ch + c] += (k * vn) * s_c,   s_c = -1 if e_c > 0, +1 if e_c < 0, else 0   (by comparison: 0 at e_c == 0 and at a NaN
+ *                                                                                          e_c, as torch's L1 backward)
+ *     ray_loss[r] += term   and / or   atomicAdd(loss_acc + r % loss_slots, term)          (both nullable)
+ * nonfinite (nullable, [0] NaN [1] Inf counters): a selected ray whose term is not finite adds nothing - no loss, no gradient - and is
+ * counted; without it the term reaches the loss and the gradient follows the comparisons.  A ray that bn_ray_shade_loss itself
+ * dropped (its shading term was not finite: loss 0, gradients 0) KEEPS its normal term: the two decisions are independent.
+ * Two launches: a one-workgroup count that WRITES count[0] (int64, device; nothing to zero before a graph replay), then one lane
+ * per ray.  n_sel is an integer and the gradient path holds no float atomic: d_acc and ray_loss repeat bit for bit.
+ * Refused (BN_EINVAL, nothing launched): NULL acc / normals / valid_normal / valid_depth / d_acc / count, R < 1 or over 2^30, C outside
+ * [4, BN_MAX_CH = 32], ch outside [0, C - 3], a lambda that is not finite, a negative stride. */
+int bn_normal_target_loss(const float *acc, int32_t C, int32_t ch, const float *normals, int64_t n_stride, const float *valid_normal,
+                          int64_t vn_stride, const float *valid_depth, int64_t vd_stride, float lambda, int64_t R, float *d_acc,
+                          float *ray_loss, float *loss_acc, int32_t loss_slots, unsigned long long *nonfinite, long long *count,
+                          void *stream);
 /* The shading of bn_ray_shade_loss under K directions at once, forward only: relighting a rendered view and the BRDF lobe of a
  * pixel from ONE geometry pass (acc, wsum do not depend on the sun; replaces create_dsm.py:44-77 and eval.py's
  * eval_pixel_variedvw, which render again per direction).  desc as above (its loss fields unused; irr must be NULL: a sun-pass
