@@ -12,20 +12,22 @@ from .rendering import render_rays, inference, get_z_vals, cal_weight  # noqa: F
 from . import functions  # noqa: F401
 from .relight import render_surface, relight, relight_image, brdf_lobe, directions  # noqa: F401
 from .shadows import render_shadow_surface, relight_shadowed, relight_image_shadowed, sun_visibility  # noqa: F401
-from .dsm import SceneFrame, Grid, point_cloud, altitude_image, DsmAccumulator, dsm_image, altitude_mae  # noqa: F401
+from .dsm import SceneFrame, Grid, point_cloud, altitude_image, DsmAccumulator, dsm_image, tie_point_dsm, altitude_mae  # noqa: F401
 from .metrics import image_psnr, image_ssim, dsm_normals, normal_angle_mae, score_view  # noqa: F401
 from .register import register_xy, apply_registration, altitude_mae_xy  # noqa: F401
 from .fill import fill_holes, apply_fill  # noqa: F401
 from .maps import ray_maps, point_normals, depth_normals, view_maps  # noqa: F401
 from . import camera  # noqa: F401
 from .camera import Rpc, view_rays, scene_bounds, ray_table, utm_zone, sun_direction, depth_priors, nearest_lines  # noqa: F401
+from .camera import ecef_geodetic  # noqa: F401
 from ._lib import set_deterministic  # noqa: F401
 
 __all__ = ["SpSBRDFNeRF", "load_model", "render_rays", "inference", "get_z_vals", "cal_weight", "functions", "set_deterministic",
            "render_surface", "relight", "relight_image", "brdf_lobe", "directions", "render_shadow_surface", "relight_shadowed",
            "relight_image_shadowed", "sun_visibility", "SceneFrame", "Grid", "point_cloud", "altitude_image", "DsmAccumulator",
-           "dsm_image", "altitude_mae", "image_psnr", "image_ssim", "dsm_normals", "normal_angle_mae", "score_view",
+           "dsm_image", "tie_point_dsm", "altitude_mae", "image_psnr", "image_ssim", "dsm_normals", "normal_angle_mae",
+           "score_view",
            "register_xy", "apply_registration", "altitude_mae_xy", "fill_holes", "apply_fill",
            "ray_maps", "point_normals", "depth_normals", "view_maps",
            "camera", "Rpc", "view_rays", "scene_bounds", "ray_table", "utm_zone", "sun_direction", "depth_priors",
-           "nearest_lines"]
+           "nearest_lines", "ecef_geodetic"]

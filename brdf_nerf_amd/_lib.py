@@ -171,6 +171,14 @@ _SIGS = {
     "bn_dsm_splat": (C.c_int, [fptr, C.c_int64, fptr, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_double,
                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, fptr, fptr, fptr]),
     "bn_dsm_resolve": (C.c_int, [fptr, C.c_int32, C.c_int32, fptr, fptr, fptr]),
+    "bn_ecef_geodetic": (C.c_int, [fptr, C.c_int64, fptr, fptr, fptr, fptr]),
+    "bn_surface_points": (C.c_int, [fptr, C.c_int64, fptr, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                    fptr, fptr, fptr]),
+    "bn_dsm_splat_points": (C.c_int, [fptr, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, fptr, fptr, fptr]),
+    "bn_dsm_splat_world": (C.c_int, [fptr, C.c_int64, fptr, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double,
+                                     C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fptr, fptr,
+                                     fptr]),
     "bn_ssim_map": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, fptr, C.c_double,
                               C.c_double, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, fptr, fptr, fptr]),
     "bn_grid_normals": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_double, fptr, fptr]),

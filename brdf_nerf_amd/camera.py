@@ -10,6 +10,7 @@ include/brdfnerf_hip.h ("The rays of a satellite view") and runs in brdf_nerf_am
   project            geodetic points -> pixels (bn_rpc_project)
   localize           pixels at an altitude -> geodetic points (bn_rpc_localize): 8 Newton iterations, no data-dependent exit
   geo_world          geodetic points -> ECEF (sat_utils.latlon_to_ecef_custom) or UTM (Krueger series to n^6) (bn_geo_world)
+  ecef_geodetic      ECEF points -> geodetic points (sat_utils.ecef_to_latlon_custom as written) (bn_ecef_geodetic)
   view_rays          get_rays + normalize_rays + get_sun_dirs of one view in one launch per chunk (bn_rpc_rays)
   scene_bounds       init_scaling_params (:238-261): the scene.loc dictionary, the centre and the range
   nearest_lines      the lines scale_depth (:396-399) samples: torch's nearest rule with its float32 scale, and its inverse
@@ -23,12 +24,12 @@ include/brdfnerf_hip.h ("The rays of a satellite view") and runs in brdf_nerf_am
 precision="reference" reproduces upstream's rounding: the WORLD origin is cast to float32 (:76-77) before the centre is
 subtracted (:550-559), which at a UTM northing of 3.3e6 m puts the origins on a 0.25 m lattice.  precision="exact" subtracts
 and divides in float64 and rounds once.  The coordinate system is this module's own parameter (`cs`, 'utm' or 'ecef');
-dsm.SceneFrame keeps refusing 'ecef'.  The UTM zone is a parameter of the scene, not taken from the first pixel of each call as
-upstream does (sat_utils.py:156-159); south=False adds no false northing, which is what upstream's "+proj=utm +zone=17R" does in
-both hemispheres.
+a dsm.SceneFrame given in place of center and range must state the same one (its zone plays no part here).  The UTM zone is
+a parameter of the scene, not taken from the first pixel of each call as upstream does (sat_utils.py:156-159); south=False adds
+no false northing, which is what upstream's "+proj=utm +zone=17R" does in both hemispheres.
 
-Not here: the file readers (JSON, GeoTIFF, the tie-point text files), image scaling, an inverse UTM
-(sat_utils.ecef_to_latlon_custom), a `group` for depth_priors (a view's priors are made once), the normals as a table column.
+Not here: the file readers (JSON, GeoTIFF, the tie-point text files), image scaling, an inverse UTM, a `group` for depth_priors
+(a view's priors are made once), the normals as a table column.
 The RPC rule is the public RPC00B definition and the UTM series Karney's; neither was checked against rpcm or pyproj.
 """
 import ctypes as C
@@ -217,12 +218,28 @@ def geo_world(lonlat, alt, cs="utm", zone=None, south=False, device=None):
     return xyz
 
 
+@torch.no_grad()
+def ecef_geodetic(xyz, device=None, want_skipped=False):
+    """Geodetic points of ECEF points ("World points of an ECEF scene" in the header; the counterpart of geo_world(cs='ecef')):
+    xyz (n, 3) metres -> lonlat float64 (n, 2) in degrees, alt float64 (n,); NaN where a point is on the axis or not finite
+    (want_skipped: also their number)."""
+    from . import functions as Fn
+    dev = _device(device, xyz)
+    xyz = torch.as_tensor(xyz, dtype=torch.float64).to(dev)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"ecef_geodetic: xyz must be (n, 3), got {tuple(xyz.shape)}")
+    _check_count(xyz.shape[0], "ecef_geodetic")
+    skipped = torch.zeros((1,), dtype=torch.int64, device=dev)
+    lonlat, alt = Fn.ecef_geodetic(xyz, skipped)
+    return (lonlat, alt, int(skipped.item())) if want_skipped else (lonlat, alt)
+
+
 def _frame(center, range, cs):
     """(center (3 floats), range) from the two values or from a dsm.SceneFrame in place of `center`."""
     from .dsm import SceneFrame
     if isinstance(center, SceneFrame):
-        if cs != "utm":
-            raise ValueError("camera: a SceneFrame states a 'utm' scene; pass center and range with cs='ecef'")
+        if center.cs != cs:
+            raise ValueError(f"camera: the SceneFrame states a {center.cs!r} scene and the call cs={cs!r}")
         center, range = center.center, center.range
     if range is None:
         raise ValueError("camera: range is missing (pass center and range, or a SceneFrame)")
@@ -540,5 +557,5 @@ def ray_table(views, images, center, range=None, cs="utm", zone=None, south=Fals
     return RayTable(rays, rgbs, **{k: torch.cat(v, 0) for k, v in cols.items()}, device=rays.device, seed=seed)
 
 
-__all__ = ["Rpc", "utm_zone", "sun_direction", "project", "localize", "geo_world", "view_rays", "scene_bounds", "ray_table",
-           "nearest_lines", "tie_priors", "depth_priors"]
+__all__ = ["Rpc", "utm_zone", "sun_direction", "project", "localize", "geo_world", "ecef_geodetic", "view_rays", "scene_bounds",
+           "ray_table", "nearest_lines", "tie_priors", "depth_priors"]

@@ -34,14 +34,16 @@
 #include <cmath>
 #include "common.h"
 #include "brdfnerf_hip.h"
+#include "geodesy.h"
 // every float64 operation below is rounded on its own (see above); the build also passes -ffp-contract=off for this file
 #pragma clang fp contract(off)
 
 namespace {
 
+// UtmK, World, geo_world, count_block and make_world: geodesy.h, shared with world.hip
+using namespace geodesy;
+
 constexpr int CAM_BLOCK = 256;
-constexpr double CAM_D2R = 3.14159265358979323846 / 180.0;        // np.pi / 180.0
-constexpr double WGS84_A = 6378137.0, WGS84_FINV = 298.257223563;
 
 struct Mono {
   double L, P, H, m4, m5, m6, m7, m8, m9, m10, m11, m12, m13, m14, m15, m16, m17, m18, m19;
@@ -118,54 +120,6 @@ __device__ __forceinline__ bool localize(const bn_rpc &R, double col, double row
   return bad;
 }
 
-// the constants of the UTM series, formed once on the host
-struct UtmK {
-  double e, k0A, alpha[6], lon0, false_north;
-};
-
-struct World {
-  int32_t cs;
-  double e2;               // ECEF: 1 - (1 - f)(1 - f)
-  UtmK utm;
-};
-
-__device__ __forceinline__ void geo_world(const World &Wd, double lon, double lat, double alt, double &x, double &y, double &z) {
-  const double rlat = lat * CAM_D2R;
-  const double sp = sin(rlat), cp = cos(rlat);
-  if (Wd.cs == BN_CS_ECEF) {
-    const double rlon = lon * CAM_D2R;
-    const double v = WGS84_A / sqrt(1.0 - Wd.e2 * sp * sp);
-    x = (v + alt) * cp * cos(rlon);
-    y = (v + alt) * cp * sin(rlon);
-    z = (v * (1.0 - Wd.e2) + alt) * sp;
-    return;
-  }
-  const UtmK &K = Wd.utm;
-  const double dl = (lon - K.lon0) * CAM_D2R;
-  const double tau = sp / cp;
-  const double t = sinh(K.e * atanh(K.e * sp));
-  const double taup = tau * sqrt(1.0 + t * t) - t * sqrt(1.0 + tau * tau);
-  const double xip = atan2(taup, cos(dl));
-  const double etap = atanh(sin(dl) / sqrt(1.0 + taup * taup));
-  // sin(2 j (xi' + i eta')), j = 1 .. 6, by the angle-addition recurrence on complex numbers (re, im)
-  const double s2 = sin(2.0 * xip), c2 = cos(2.0 * xip), sh2 = sinh(2.0 * etap), ch2 = cosh(2.0 * etap);
-  const double zr = s2 * ch2, zi = c2 * sh2;        // sin(2 zeta)
-  const double wr = c2 * ch2, wi = -(s2 * sh2);     // cos(2 zeta)
-  double Sr = zr, Si = zi, Cr = wr, Ci = wi;
-  double xi = xip, eta = etap;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    xi = xi + K.alpha[j] * Sr;
-    eta = eta + K.alpha[j] * Si;
-    const double nSr = (Sr * wr - Si * wi) + (Cr * zr - Ci * zi), nSi = (Sr * wi + Si * wr) + (Cr * zi + Ci * zr);
-    const double nCr = (Cr * wr - Ci * wi) - (Sr * zr - Si * zi), nCi = (Cr * wi + Ci * wr) - (Sr * zi + Si * zr);
-    Sr = nSr; Si = nSi; Cr = nCr; Ci = nCi;
-  }
-  x = 500000.0 + K.k0A * eta;
-  y = K.false_north + K.k0A * xi;
-  z = alt;
-}
-
 // the pixel of ray r: grid mode (cols == NULL) or the arrays
 __device__ __forceinline__ void pixel_of(const double *cols, const double *rows, int32_t W, int64_t r, double &col, double &row) {
   if (cols) {
@@ -175,17 +129,6 @@ __device__ __forceinline__ void pixel_of(const double *cols, const double *rows,
     col = (double)(r % W);
     row = (double)(r / W);
   }
-}
-
-// the block's counted rows, one integer atomic (every thread of the block calls this)
-__device__ __forceinline__ void count_block(bool bad, unsigned long long *counts) {
-  __shared__ unsigned int block_bad;
-  if (threadIdx.x == 0) block_bad = 0;
-  __syncthreads();
-  const unsigned long long ballot = __ballot(bad);
-  if ((threadIdx.x & 63) == 0 && ballot) atomicAdd(&block_bad, (unsigned int)__popcll(ballot));       // LDS, integer
-  __syncthreads();
-  if (threadIdx.x == 0 && block_bad) atomicAdd(counts, (unsigned long long)block_bad);
 }
 
 __global__ __launch_bounds__(CAM_BLOCK)
@@ -406,28 +349,6 @@ bool rpc_ok(const bn_rpc *rpc) {
   for (int i = 5; i < 10; ++i)
     if (v[i] == 0.0) return false;
   return true;
-}
-
-// World of (cs, zone, south): the WGS84 constants of both coordinate systems
-World make_world(int32_t cs, int32_t zone, int32_t south) {
-  World w;
-  const double f = 1.0 / WGS84_FINV;
-  w.cs = cs;
-  w.e2 = 1.0 - (1.0 - f) * (1.0 - f);
-  const double n = f / (2.0 - f), n2 = n * n;
-  UtmK &K = w.utm;
-  K.e = std::sqrt(f * (2.0 - f));
-  K.k0A = 0.9996 * (WGS84_A / (1.0 + n) * (1.0 + n2 / 4.0 + n2 * n2 / 64.0 + n2 * n2 * n2 / 256.0));
-  // Karney 2011, eq. 35: alpha_j / n^j as polynomials in n (highest power first), over a common denominator
-  K.alpha[0] = n * (((((31564.0 * n - 66675.0) * n + 34440.0) * n + 47250.0) * n - 100800.0) * n + 75600.0) / 151200.0;
-  K.alpha[1] = n2 * ((((-1983433.0 * n + 863232.0) * n + 748608.0) * n - 1161216.0) * n + 524160.0) / 1935360.0;
-  K.alpha[2] = n2 * n * (((670412.0 * n + 406647.0) * n - 533952.0) * n + 184464.0) / 725760.0;
-  K.alpha[3] = n2 * n2 * ((6601661.0 * n - 7732800.0) * n + 2230245.0) / 7257600.0;
-  K.alpha[4] = n2 * n2 * n * (-13675556.0 * n + 3438171.0) / 7983360.0;
-  K.alpha[5] = n2 * n2 * n2 * 212378941.0 / 319334400.0;
-  K.lon0 = 6.0 * zone - 183.0;
-  K.false_north = south ? 10000000.0 : 0.0;
-  return w;
 }
 
 constexpr int64_t CAM_MAX_RAYS = (int64_t)1 << 30;

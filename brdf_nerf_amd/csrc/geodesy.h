@@ -1,0 +1,136 @@
+// The float64 geodesy shared by camera.hip (geodetic -> world: the rays and the depth priors of a view) and world.hip (world ->
+// east, north, altitude: the surface model of an ECEF scene): the WGS84 constants as the host forms them, the forward rule of
+// include/brdfnerf_hip.h ("The rays of a satellite view", step 4) and the inverse ("World points of an ECEF scene").  Every
+// operation is rounded on its own: both files are built with fp contraction off and the pragma below covers the functions here
+// wherever they are included.  The device's float64 sin / cos / atan2 / atanh / sinh / cosh are not bit-specified: what comes out
+// of them is held to a bound, not to bits.
+#pragma once
+#include <cmath>
+#include "common.h"
+#pragma clang fp contract(off)
+
+namespace geodesy {
+
+constexpr double CAM_D2R = 3.14159265358979323846 / 180.0;        // np.pi / 180.0
+constexpr double CAM_PI = 3.14159265358979323846;                 // np.pi
+constexpr double WGS84_A = 6378137.0, WGS84_FINV = 298.257223563;
+
+// the constants of the UTM series, formed once on the host
+struct UtmK {
+  double e, k0A, alpha[6], lon0, false_north;
+};
+
+struct World {
+  int32_t cs;
+  double e2;               // ECEF: 1 - (1 - f)(1 - f)
+  UtmK utm;
+};
+
+__device__ __forceinline__ void geo_world(const World &Wd, double lon, double lat, double alt, double &x, double &y, double &z) {
+  const double rlat = lat * CAM_D2R;
+  const double sp = sin(rlat), cp = cos(rlat);
+  if (Wd.cs == BN_CS_ECEF) {
+    const double rlon = lon * CAM_D2R;
+    const double v = WGS84_A / sqrt(1.0 - Wd.e2 * sp * sp);
+    x = (v + alt) * cp * cos(rlon);
+    y = (v + alt) * cp * sin(rlon);
+    z = (v * (1.0 - Wd.e2) + alt) * sp;
+    return;
+  }
+  const UtmK &K = Wd.utm;
+  const double dl = (lon - K.lon0) * CAM_D2R;
+  const double tau = sp / cp;
+  const double t = sinh(K.e * atanh(K.e * sp));
+  const double taup = tau * sqrt(1.0 + t * t) - t * sqrt(1.0 + tau * tau);
+  const double xip = atan2(taup, cos(dl));
+  const double etap = atanh(sin(dl) / sqrt(1.0 + taup * taup));
+  // sin(2 j (xi' + i eta')), j = 1 .. 6, by the angle-addition recurrence on complex numbers (re, im)
+  const double s2 = sin(2.0 * xip), c2 = cos(2.0 * xip), sh2 = sinh(2.0 * etap), ch2 = cosh(2.0 * etap);
+  const double zr = s2 * ch2, zi = c2 * sh2;        // sin(2 zeta)
+  const double wr = c2 * ch2, wi = -(s2 * sh2);     // cos(2 zeta)
+  double Sr = zr, Si = zi, Cr = wr, Ci = wi;
+  double xi = xip, eta = etap;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    xi = xi + K.alpha[j] * Sr;
+    eta = eta + K.alpha[j] * Si;
+    const double nSr = (Sr * wr - Si * wi) + (Cr * zr - Ci * zi), nSi = (Sr * wi + Si * wr) + (Cr * zi + Ci * zr);
+    const double nCr = (Cr * wr - Ci * wi) - (Sr * zr - Si * zi), nCi = (Cr * wi + Ci * wr) - (Sr * zi + Si * zr);
+    Sr = nSr; Si = nSi; Cr = nCr; Ci = nCi;
+  }
+  x = 500000.0 + K.k0A * eta;
+  y = K.false_north + K.k0A * xi;
+  z = alt;
+}
+
+// the constants of sat_utils.ecef_to_latlon_custom (:131-137), formed once on the host
+struct EcefK {
+  double a, b, esq, k1, k2;        // k1 = (ep ep) b, k2 = esq a
+};
+
+// "World points of an ECEF scene" in the header: Bowring's one-step formula as upstream writes it, the cubes as (s s) s.
+// -> true when the point is refused: on the axis (p == 0), or x, y, z, lat or alt not finite.  lon, lat in degrees.
+__device__ __forceinline__ bool ecef_geodetic(const EcefK &K, double x, double y, double z, double &lon, double &lat, double &alt) {
+  const double p = sqrt(x * x + y * y);
+  const double th = atan2(K.a * z, K.b * p);
+  const double s = sin(th), c = cos(th);
+  const double rlon = atan2(y, x);
+  const double rlat = atan2(z + K.k1 * ((s * s) * s), p - K.k2 * ((c * c) * c));
+  const double sl = sin(rlat);
+  const double N = K.a / sqrt(1.0 - K.esq * (sl * sl));
+  alt = p / cos(rlat) - N;
+  lon = rlon * 180.0 / CAM_PI;
+  lat = rlat * 180.0 / CAM_PI;
+  return p == 0.0 || !(isfinite(x) && isfinite(y) && isfinite(z) && isfinite(rlat) && isfinite(alt));
+}
+
+// the block's counted rows, one integer atomic (every thread of the block calls this)
+__device__ __forceinline__ void count_block(bool bad, unsigned long long *counts) {
+  __shared__ unsigned int block_bad;
+  if (threadIdx.x == 0) block_bad = 0;
+  __syncthreads();
+  const unsigned long long ballot = __ballot(bad);
+  if ((threadIdx.x & 63) == 0 && ballot) atomicAdd(&block_bad, (unsigned int)__popcll(ballot));       // LDS, integer
+  __syncthreads();
+  if (threadIdx.x == 0 && block_bad) atomicAdd(counts, (unsigned long long)block_bad);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+// World of (cs, zone, south): the WGS84 constants of both coordinate systems
+inline World make_world(int32_t cs, int32_t zone, int32_t south) {
+  World w;
+  const double f = 1.0 / WGS84_FINV;
+  w.cs = cs;
+  w.e2 = 1.0 - (1.0 - f) * (1.0 - f);
+  const double n = f / (2.0 - f), n2 = n * n;
+  UtmK &K = w.utm;
+  K.e = std::sqrt(f * (2.0 - f));
+  K.k0A = 0.9996 * (WGS84_A / (1.0 + n) * (1.0 + n2 / 4.0 + n2 * n2 / 64.0 + n2 * n2 * n2 / 256.0));
+  // Karney 2011, eq. 35: alpha_j / n^j as polynomials in n (highest power first), over a common denominator
+  K.alpha[0] = n * (((((31564.0 * n - 66675.0) * n + 34440.0) * n + 47250.0) * n - 100800.0) * n + 75600.0) / 151200.0;
+  K.alpha[1] = n2 * ((((-1983433.0 * n + 863232.0) * n + 748608.0) * n - 1161216.0) * n + 524160.0) / 1935360.0;
+  K.alpha[2] = n2 * n * (((670412.0 * n + 406647.0) * n - 533952.0) * n + 184464.0) / 725760.0;
+  K.alpha[3] = n2 * n2 * ((6601661.0 * n - 7732800.0) * n + 2230245.0) / 7257600.0;
+  K.alpha[4] = n2 * n2 * n * (-13675556.0 * n + 3438171.0) / 7983360.0;
+  K.alpha[5] = n2 * n2 * n2 * 212378941.0 / 319334400.0;
+  K.lon0 = 6.0 * zone - 183.0;
+  K.false_north = south ? 10000000.0 : 0.0;
+  return w;
+}
+
+// upstream's truncated eccentricity, NOT the one of 1 / 298.257223563 that make_world uses (6e-15 apart, relative)
+inline EcefK make_ecef_k() {
+  EcefK k;
+  const double e = 8.1819190842622e-2;
+  k.a = WGS84_A;
+  const double asq = k.a * k.a;
+  k.esq = e * e;
+  k.b = std::sqrt(asq * (1.0 - k.esq));
+  const double bsq = k.b * k.b;
+  const double ep = std::sqrt((asq - bsq) / bsq);
+  k.k1 = (ep * ep) * k.b;
+  k.k2 = k.esq * k.a;
+  return k;
+}
+
+}  // namespace geodesy

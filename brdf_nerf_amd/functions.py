@@ -748,6 +748,83 @@ def dsm_splat(rays, depth, center, rng, xoff, yoff, resolution, radius, footprin
     return acc
 
 
+def _ray_rows(rays, depth):
+    R = rays.shape[0]
+    assert rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] >= 6
+    assert depth.is_cuda and depth.dtype == torch.float32 and depth.shape == (R,)
+    rays = rays if rays.stride(1) == 1 else rays.contiguous()
+    return rays, depth.contiguous(), R, (rays.stride(0) if R > 1 else rays.shape[1])       # (one row: its stride is not read)
+
+
+def _dsm_acc(acc, skipped):
+    assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] == 2 and acc.is_contiguous()
+    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    return acc.shape[0], acc.shape[1]
+
+
+def ecef_geodetic(xyz, skipped):
+    """Geodetic points of ECEF points (bn_ecef_geodetic): xyz (n, 3) float64 -> lonlat (n, 2) in degrees, alt (n,) float64, NaN
+    where a point is refused (on the axis or not finite); skipped (1,) int64 on the device, accumulated into."""
+    assert xyz.is_cuda and xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.shape[1] == 3
+    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    xyz = xyz.contiguous()
+    n = xyz.shape[0]
+    lonlat = torch.empty((n, 2), dtype=torch.float64, device=xyz.device)
+    alt = torch.empty((n,), dtype=torch.float64, device=xyz.device)
+    if n == 0:
+        return lonlat, alt
+    with torch.cuda.device(xyz.device):
+        L.check(L.lib().bn_ecef_geodetic(_p(xyz), n, _p(lonlat), _p(alt), _p(skipped), _stream()), "bn_ecef_geodetic")
+    return lonlat, alt
+
+
+def surface_points(rays, depth, center, rng, cs, zone, south, skipped):
+    """(east, north, altitude) of R rays' surface points (bn_surface_points): rays (R, >= 6) float32 rows with unit inner stride,
+    depth (R,) float32; cs BN_CS_ECEF or BN_CS_UTM, the scene's zone -> float64 (R, 3), NaN where a row is refused; skipped (1,)
+    int64 on the device, accumulated into."""
+    rays, depth, R, stride = _ray_rows(rays, depth)
+    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    enz = torch.empty((R, 3), dtype=torch.float64, device=rays.device)
+    if R == 0:
+        return enz
+    c = (C.c_double * 3)(*[float(v) for v in center])
+    with torch.cuda.device(rays.device):
+        L.check(L.lib().bn_surface_points(C.c_void_p(rays.data_ptr()), stride, _p(depth), R, c, float(rng), int(cs), int(zone),
+                                          int(south), _p(enz), _p(skipped), _stream()), "bn_surface_points")
+    return enz
+
+
+def dsm_splat_points(enz, xoff, yoff, resolution, radius, footprint, acc, skipped):
+    """World points that already are (east, north, altitude) splatted into a DSM accumulator (bn_dsm_splat_points): enz (n, >= 3)
+    float64 rows with unit inner stride; acc and skipped as dsm_splat."""
+    assert enz.is_cuda and enz.dtype == torch.float64 and enz.dim() == 2 and enz.shape[1] >= 3
+    H, W = _dsm_acc(acc, skipped)
+    if enz.shape[0] == 0:
+        return acc
+    if enz.stride(1) != 1:
+        enz = enz.contiguous()
+    with torch.cuda.device(enz.device):
+        L.check(L.lib().bn_dsm_splat_points(C.c_void_p(enz.data_ptr()), enz.stride(0) if enz.shape[0] > 1 else enz.shape[1], enz.shape[0],
+                                            float(xoff), float(yoff), float(resolution), W, H, int(radius), int(footprint), _p(acc),
+                                            _p(skipped), _stream()), "bn_dsm_splat_points")
+    return acc
+
+
+def dsm_splat_world(rays, depth, center, rng, xoff, yoff, resolution, radius, footprint, cs, zone, south, acc, skipped):
+    """dsm_splat for a scene whose world points are `cs` (bn_dsm_splat_world): ray -> world point -> (east, north, altitude) ->
+    deposit in one launch."""
+    rays, depth, R, stride = _ray_rows(rays, depth)
+    H, W = _dsm_acc(acc, skipped)
+    if R == 0:
+        return acc
+    c = (C.c_double * 3)(*[float(v) for v in center])
+    with torch.cuda.device(rays.device):
+        L.check(L.lib().bn_dsm_splat_world(C.c_void_p(rays.data_ptr()), stride, _p(depth), R, c, float(rng), float(xoff),
+                                           float(yoff), float(resolution), W, H, int(radius), int(footprint), int(cs), int(zone),
+                                           int(south), _p(acc), _p(skipped), _stream()), "bn_dsm_splat_world")
+    return acc
+
+
 def dsm_resolve(acc, want_count=True):
     """Mean altitude per cell of a DSM accumulator (bn_dsm_resolve): acc (H, W, 2) int64 -> dsm (H, W) float32, NaN where no
     point fell, and count (H, W) int32 (or None)."""

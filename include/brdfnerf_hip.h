@@ -839,6 +839,57 @@ int bn_tie_priors(const bn_rpc *rpc, const int32_t *px, const int32_t *owner, co
                   double range, int32_t round_f32, double cmin, double cmax, double corrscale, double stdscale, double margin,
                   double std_span, float *valid, float *depths, float *depth_std, float *rays, float *points, float *valid_full,
                   float *tie_rays, unsigned long long *counts, void *stream);
+/* World points of an ECEF scene (additive to ABI 7): what takes a point of a scene whose world coordinates are ECEF to (east,
+ * north, altitude), so that the surface model - bn_dsm_splat's accumulator, the altitude image, the altitude MAE - is served for
+ * such a scene as it is for a UTM one.  The reference does it on the host: sat_utils.ecef_to_latlon_custom (sat_utils.py:127-146),
+ * Bowring's one-step formula, then utm_from_latlon through pyproj (datasets/satellite_rgb_dep.py:629-631).  world.hip and the
+ * geodesy.h it shares with camera.hip are compiled with fp contraction off: all of it is float64 and every operation is rounded
+ * on its own.  The constants are formed on the host exactly as upstream forms them, with its TRUNCATED eccentricity - not the one
+ * of step 4 above (f = 1 / 298.257223563; the two differ by 6e-15 relative, which moves no output by more than 4e-9 m).  Geodetic
+ * -> ECEF -> geodetic does not close: the single step leaves 7.2e-7 m in latitude, 4.6e-9 m in longitude and 8.6e-7 m in altitude
+ * over |lat| <= 80 degrees and altitudes of -500 to 9000 m.  Upstream's rule is reproduced as written; no exact variant is served.
+ *   a = 6378137.0 ; e = 8.1819190842622e-2 ; asq = a a ; esq = e e
+ *   b = sqrt(asq (1 - esq)) ; bsq = b b ; ep = sqrt((asq - bsq) / bsq)
+ *   k1 = (ep ep) b ; k2 = esq a
+ *   p   = sqrt(x x + y y)
+ *   th  = atan2(a z, b p) ; s = sin(th) ; c = cos(th)
+ *   lon = atan2(y, x)
+ *   lat = atan2(z + k1 ((s s) s), p - k2 ((c c) c))
+ *   sl  = sin(lat) ; N = a / sqrt(1 - esq (sl sl))
+ *   alt = p / cos(lat) - N
+ *   lon_deg = lon 180 / pi ; lat_deg = lat 180 / pi          (left to right)
+ *   (east, north) = the UTM series of step 4 above at (lon_deg, lat_deg), zone, south ; z = alt
+ * Upstream writes the cubes as np.sin(th) ** 3, a pow; (s s) s differs from it by roundings only (at most 3.2e-9 m in latitude and
+ * 7.5e-9 m in altitude over |lat| <= 80 degrees, the longitude is equal).  The zone is a parameter of the scene, as in step 4;
+ * south = 0 adds no false northing.  The device's float64 atan2, sin and cos are not bit-specified: as for bn_geo_world the
+ * results are held to the numpy statement within 1e-6 m, not to bits.
+ * A point is REFUSED - it gives NaN, deposits nothing and is counted in skipped[0] - when p == 0 (on the axis), or when x, y, z,
+ * lat, alt, east or north is not finite; where it is deposited into a DSM also when |alt| >= 2^23 m, bn_dsm_splat's rule.
+ * upstream's get_dsm_from_nerf_prediction converts an ECEF cloud TWICE (:649-651 runs utm_from_latlon on what :629-631 already
+ * returned as easts and norths); this project converts once, the reading eval.py:170 takes for the altitude image.
+ *
+ *   bn_ecef_geodetic     xyz float64 [n][3] -> lonlat float64 [n][2] in degrees, alt float64 [n]: the inverse alone, the
+ *                        counterpart of bn_geo_world with cs = BN_CS_ECEF.
+ *   bn_surface_points    P = (o + d depth) range + center, formed as bn_dsm_splat forms it; cs = BN_CS_ECEF: P through the rule;
+ *                        cs = BN_CS_UTM: P as it is.  enz float64 [R][3] = (east, north, altitude), a refused row is NaN.
+ *   bn_dsm_splat_points  the cell, footprint and deposit of bn_dsm_splat for n given points: enz float64 rows of stride >= 3
+ *                        doubles = (east, north, altitude).  Covers the tie points of a view (datasets/cal_rmse_depth.py:15-64).
+ *   bn_dsm_splat_world   bn_dsm_splat's arguments and (cs, zone, south): ray -> world point -> deposit in ONE launch, no cloud
+ *                        in between.  It runs the very device functions of the two entries above, so its accumulator is
+ *                        theirs bit for bit; for cs = BN_CS_UTM it is bn_dsm_splat's bit for bit.
+ * One lane per ray or point.  acc and skipped as in bn_dsm_splat (the CALLER zeroes them; calls accumulate); skipped[0] is summed
+ * per block and added with ONE integer atomic.  Integer atomics only: no float atomic.
+ * Refused (BN_EINVAL): NULL pointers, a negative count, ray_stride < 6 or stride < 3, another cs, zone outside [1, 60] (read for
+ * cs = BN_CS_UTM too), south other than 0 or 1, a non-finite frame or grid origin, and the grid, radius and footprint refusals of
+ * bn_dsm_splat. */
+int bn_ecef_geodetic(const double *xyz, int64_t n, double *lonlat, double *alt, unsigned long long *skipped, void *stream);
+int bn_surface_points(const float *rays, int64_t ray_stride, const float *depth, int64_t R, const double *center, double range,
+                      int32_t cs, int32_t zone, int32_t south, double *enz, unsigned long long *skipped, void *stream);
+int bn_dsm_splat_points(const double *enz, int64_t stride, int64_t n, double xoff, double yoff, double resolution, int32_t W, int32_t H,
+                        int32_t radius, int32_t footprint, long long *acc, unsigned long long *skipped, void *stream);
+int bn_dsm_splat_world(const float *rays, int64_t ray_stride, const float *depth, int64_t R, const double *center, double range,
+                       double xoff, double yoff, double resolution, int32_t W, int32_t H, int32_t radius, int32_t footprint, int32_t cs,
+                       int32_t zone, int32_t south, long long *acc, unsigned long long *skipped, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
