@@ -17,6 +17,7 @@ from .metrics import image_psnr, image_ssim, dsm_normals, normal_angle_mae, scor
 from .register import register_xy, apply_registration, altitude_mae_xy  # noqa: F401
 from .fill import fill_holes, apply_fill  # noqa: F401
 from .maps import ray_maps, point_normals, depth_normals, view_maps  # noqa: F401
+from .ortho import OrthoAccumulator, ortho_image  # noqa: F401
 from . import camera  # noqa: F401
 from .camera import Rpc, view_rays, scene_bounds, ray_table, utm_zone, sun_direction, depth_priors, nearest_lines  # noqa: F401
 from .camera import ecef_geodetic  # noqa: F401
@@ -28,6 +29,6 @@ __all__ = ["SpSBRDFNeRF", "load_model", "render_rays", "inference", "get_z_vals"
            "dsm_image", "tie_point_dsm", "altitude_mae", "image_psnr", "image_ssim", "dsm_normals", "normal_angle_mae",
            "score_view",
            "register_xy", "apply_registration", "altitude_mae_xy", "fill_holes", "apply_fill",
-           "ray_maps", "point_normals", "depth_normals", "view_maps",
+           "ray_maps", "point_normals", "depth_normals", "view_maps", "OrthoAccumulator", "ortho_image",
            "camera", "Rpc", "view_rays", "scene_bounds", "ray_table", "utm_zone", "sun_direction", "depth_priors",
            "nearest_lines", "ecef_geodetic"]

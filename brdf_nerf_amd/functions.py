@@ -825,6 +825,70 @@ def dsm_splat_world(rays, depth, center, rng, xoff, yoff, resolution, radius, fo
     return acc
 
 
+def _ortho_grid(args, cs, zone, south):
+    center, rng, xoff, yoff, resolution, radius, footprint = args
+    return ((C.c_double * 3)(*[float(v) for v in center]), float(rng), float(xoff), float(yoff), float(resolution)), \
+        (int(radius), int(footprint), int(cs), int(zone), int(south))
+
+
+def ortho_top(rays, depth, center, rng, xoff, yoff, resolution, radius, footprint, cs, zone, south, top, skipped):
+    """Pass 1 of the orthorectified maps (bn_ortho_top): top (H, W) int64, filled with BN_ORTHO_EMPTY by the caller, takes the
+    maximum of the quantised altitudes over every ray's footprint; rays, depth, the frame and the grid as dsm_splat_world; skipped
+    (1,) int64 on the device, accumulated into."""
+    rays, depth, R, stride = _ray_rows(rays, depth)
+    assert top.is_cuda and top.dtype == torch.int64 and top.dim() == 2 and top.is_contiguous()
+    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    if R == 0:
+        return top
+    H, W = top.shape
+    (c, rng, xoff, yoff, resolution), tail = _ortho_grid((center, rng, xoff, yoff, resolution, radius, footprint), cs, zone, south)
+    with torch.cuda.device(rays.device):
+        L.check(L.lib().bn_ortho_top(C.c_void_p(rays.data_ptr()), stride, _p(depth), R, c, rng, xoff, yoff, resolution, W, H, *tail,
+                                     _p(top), _p(skipped), _stream()), "bn_ortho_top")
+    return top
+
+
+def ortho_splat(rays, depth, center, rng, xoff, yoff, resolution, radius, footprint, cs, zone, south, features, top, band_q, acc,
+                counters):
+    """Pass 2 of the orthorectified maps (bn_ortho_splat): features (R, E) float32 rows with unit channel stride (a column slice of
+    a wider tensor is read in place; None with E == 0) deposited with the altitude into acc (H, W, 2 + E) int64 = (sum_z, count,
+    sum_0 ...), accumulated into; top (H, W) int64 of ortho_top or None (mean mode), band_q in units of 2^-20 m; counters (3,)
+    int64 on the device = (bad points, bad features, culled deposits), accumulated into."""
+    rays, depth, R, stride = _ray_rows(rays, depth)
+    assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] >= 2 and acc.is_contiguous()
+    H, W, E = acc.shape[0], acc.shape[1], acc.shape[2] - 2
+    assert counters.is_cuda and counters.dtype == torch.int64 and counters.numel() == 3 and counters.is_contiguous()
+    assert top is None or (top.is_cuda and top.dtype == torch.int64 and top.shape == (H, W) and top.is_contiguous())
+    if E == 0:
+        assert features is None or (features.dim() == 2 and features.shape == (R, 0))
+        fp, fs = None, 0
+    else:
+        assert features is not None and features.is_cuda and features.dtype == torch.float32 and features.shape == (R, E)
+        if features.stride(1) != 1 and E > 1:
+            features = features.contiguous()
+        fp, fs = C.c_void_p(features.data_ptr()), (features.stride(0) if R > 1 else E)       # (one row: its stride is not read)
+    if R == 0:
+        return acc
+    (c, rng, xoff, yoff, resolution), tail = _ortho_grid((center, rng, xoff, yoff, resolution, radius, footprint), cs, zone, south)
+    with torch.cuda.device(rays.device):
+        L.check(L.lib().bn_ortho_splat(C.c_void_p(rays.data_ptr()), stride, _p(depth), R, c, rng, xoff, yoff, resolution, W, H, *tail,
+                                       fp, fs, E, _p(top), int(band_q), _p(acc), _p(counters), _stream()), "bn_ortho_splat")
+    return acc
+
+
+def ortho_resolve(acc, want_count=True):
+    """The means of an accumulator of orthorectified maps (bn_ortho_resolve): acc (H, W, 2 + E) int64 -> maps (E, H, W) float32,
+    dsm (H, W) float32, both NaN where no point fell, and count (H, W) int32 (or None)."""
+    assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] >= 2 and acc.is_contiguous()
+    H, W, E = acc.shape[0], acc.shape[1], acc.shape[2] - 2
+    maps = torch.empty((E, H, W), dtype=torch.float32, device=acc.device)
+    dsm = torch.empty((H, W), dtype=torch.float32, device=acc.device)
+    count = torch.empty((H, W), dtype=torch.int32, device=acc.device) if want_count else None
+    with torch.cuda.device(acc.device):
+        L.check(L.lib().bn_ortho_resolve(_p(acc), W, H, E, _p(maps) if E else None, _p(dsm), _p(count), _stream()), "bn_ortho_resolve")
+    return maps, dsm, count
+
+
 def dsm_resolve(acc, want_count=True):
     """Mean altitude per cell of a DSM accumulator (bn_dsm_resolve): acc (H, W, 2) int64 -> dsm (H, W) float32, NaN where no
     point fell, and count (H, W) int32 (or None)."""

@@ -890,6 +890,57 @@ int bn_dsm_splat_points(const double *enz, int64_t stride, int64_t n, double xof
 int bn_dsm_splat_world(const float *rays, int64_t ray_stride, const float *depth, int64_t R, const double *center, double range,
                        double xoff, double yoff, double resolution, int32_t W, int32_t H, int32_t radius, int32_t footprint, int32_t cs,
                        int32_t zone, int32_t south, long long *acc, unsigned long long *skipped, void *stream);
+/* Orthorectified maps of a view (additive to ABI 7): the ray-level maps of a view (rgb, albedo, normals, BRDF parameters) splatted
+ * into the grid of the DSM, channel by channel, so that they lie on the DSM's cells and fuse over views as it does.  The feature
+ * channels have NO upstream counterpart - the reference rasterises the altitude alone (plyflatten, datasets/satellite_rgb_dep.py:
+ * 636-699) - so the rule below is this project's own and there is nothing to check it against but its statement.  Its altitude
+ * part IS bn_dsm_splat's rule: the point p, the cell (j, i), the footprint, the skip rule of a bad point (p not finite or
+ * |p.z| >= 2^23 m; cs = BN_CS_ECEF: also what bn_dsm_splat_world refuses) and q = llrint(p.z 2^20) are exactly those of
+ * bn_dsm_splat, for cs = BN_CS_ECEF those of bn_dsm_splat_world - the same device functions, float64, every operation rounded on
+ * its own, no fused multiply-add.  An oblique view reaches a cell along a building's edge at several heights (roof, facade,
+ * ground); the mean that is right for the altitude mixes their colours, hence the optional top-surface pass.
+ *
+ * bn_ortho_top (pass 1, top mode only): top int64 [H][W], which the CALLER fills with BN_ORTHO_EMPTY = INT64_MIN.  Every
+ *   footprint cell of a ray inside the grid takes top = max(top, q), a signed 64-bit integer atomic max.  A bad point adds 1 to
+ *   skipped[0].  Arguments as bn_dsm_splat_world.
+ * bn_ortho_splat (pass 2): the arguments of bn_dsm_splat_world and
+ *     features  float32 [R] rows of E channels, row stride feature_stride >= E floats, unit channel stride (NULL with E == 0)
+ *     E         channels, in [0, BN_ORTHO_MAX_CHANNELS]
+ *     top       the finished grid of pass 1, or NULL (mean mode)
+ *     band_q    int64 >= 0, in units of 2^-20 m (a value above 2^62 acts as 2^62: |q| <= 2^43, so every band from 2^44 keeps all)
+ *     acc       int64 [H][W][2 + E] = (sum_z, count, sum_0 .. sum_{E-1}) per cell, 16-byte aligned, which the CALLER zeroes; calls
+ *               accumulate into it
+ *     counters  uint64 [3] = (bad points, bad features, culled deposits), which the caller zeroes
+ *   Per ray: a bad point deposits nothing and adds 1 to counters[0].  Otherwise f_e = llrint((double)x_e 2^24) for each channel; a
+ *   ray with any x_e that is not finite or has |x_e| >= 2^16 deposits nothing and adds 1 to counters[1] (a ray with a bad point AND
+ *   a bad feature counts as a bad point only).  Then |f_e| <= 2^40: a cell's sum cannot overflow below 2^22 points.
+ *   For each footprint cell inside the grid, tested cell by cell on its own:
+ *     if top is given and q + band_q < top[cell]: the cell gets nothing from this ray and counters[2] gains 1 (the comparison is
+ *       written this way so that an EMPTY cell passes everything and nothing overflows);
+ *     otherwise sum_z += q, count += 1, sum_e += f_e, all integer atomic adds (two's complement).
+ *   There is no float atomic in this path; each counter goes out as one integer atomic per block.
+ * bn_ortho_resolve: maps [E][H][W], maps[e] = (float)((double)sum_e / (double)count 2^-24); dsm [H][W] as bn_dsm_resolve gives it;
+ *   a cell with count == 0 is NaN in all of them; count [H][W] int32 (nullable), saturating at 2^31 - 1.
+ *
+ * Consequences.  With E == 0 and top == NULL acc is bn_dsm_splat's accumulator bit for bit (bn_dsm_splat_world's for
+ * cs = BN_CS_ECEF).  Every output bit depends on the SET of rays alone - not on their order, on how they are split over calls,
+ * views or devices (top merges by a MAX, acc and the counters by a SUM all-reduce) - provided pass 1 has seen every ray before
+ * pass 2 starts.  top == NULL is the mean over all points of a cell; top mode with a band of b metres (band_q = llrint(b 2^20))
+ * keeps, per cell, the points within b of the highest point that reaches that cell.  The mean of unit normals is not a unit
+ * vector and is not renormalised.
+ * Refused (BN_EINVAL, nothing launched, buffers untouched): NULL required pointers, E outside [0, BN_ORTHO_MAX_CHANNELS],
+ * feature_stride < E, band_q < 0, E > 0 without features (maps in bn_ortho_resolve), acc not 16-byte aligned, and everything
+ * bn_dsm_splat_world refuses. */
+#define BN_ORTHO_MAX_CHANNELS 32
+#define BN_ORTHO_EMPTY INT64_MIN
+int bn_ortho_top(const float *rays, int64_t ray_stride, const float *depth, int64_t R, const double *center, double range, double xoff,
+                 double yoff, double resolution, int32_t W, int32_t H, int32_t radius, int32_t footprint, int32_t cs, int32_t zone,
+                 int32_t south, long long *top, unsigned long long *skipped, void *stream);
+int bn_ortho_splat(const float *rays, int64_t ray_stride, const float *depth, int64_t R, const double *center, double range,
+                   double xoff, double yoff, double resolution, int32_t W, int32_t H, int32_t radius, int32_t footprint, int32_t cs,
+                   int32_t zone, int32_t south, const float *features, int64_t feature_stride, int32_t E, const long long *top,
+                   long long band_q, long long *acc, unsigned long long *counters, void *stream);
+int bn_ortho_resolve(const long long *acc, int32_t W, int32_t H, int32_t E, float *maps, float *dsm, int32_t *count, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
