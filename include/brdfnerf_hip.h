@@ -198,8 +198,9 @@ int bn_field_backward(const bn_field_desc *desc, const bn_field_params *params, 
  * stash with the pre-activation gradients; BN_BWD_WGRAD_TRUNK = the weight gradients of the trunk layers (the leading,
  * contiguous share of a flat parameter buffer in state_dict order); BN_BWD_WGRAD_HEADS = those of the (folded) head first
  * layers, the feats layer and the extra-input columns; BN_BWD_SKINNY = the one- to four-row matrices (sigma head, learned
- * normal, second head layers) and d_t_embed.  The parts of one backward are called in this order on one stream; the
- * deterministic mode takes BN_BWD_ALL only. */
+ * normal, second head layers) and d_t_embed.  The parts of one backward are called in this order on one stream.
+ * Every mask is served whatever bn_set_deterministic says (the switch changes nothing: the slab sums run in a fixed order);
+ * a gradient is written by the jobs of ONE part, so it is final once the call that carries that part has run. */
 enum { BN_BWD_CHAIN = 1, BN_BWD_WGRAD_TRUNK = 2, BN_BWD_WGRAD_HEADS = 4, BN_BWD_SKINNY = 8, BN_BWD_ALL = 15 };
 int bn_field_backward_parts(const bn_field_desc *desc, const bn_field_params *params, const void *packed,
                             const bn_points *pts, const float *out, const float *d_out, void *stash,

@@ -548,19 +548,29 @@ def _lean_cfgs():
     }
 
 
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("name", list(_lean_cfgs()))
-def test_lean_step_matches_general_step_on_the_same_draws(name, dtype):
+def _lean_rows():
+    """(name, dtype, S, G) and the test ids: every model at S = G = 16 (ids `name-dtype`), and one S != G row for the Lambertian
+    model and for the one with analytic normals - with S = G a kernel of the two-block backward that reads the first block's
+    sample count where the second's belongs computes the same thing."""
+    rows = [(n, d, 16, 16) for d in ("fp32", "bf16") for n in _lean_cfgs()]
+    rows += [(n, d, 24, 8) for d in ("fp32", "bf16") for n in ("lambert", "rpv111_nan")]
+    return rows, [f"{n}-{d}" + ("" if (S, G) == (16, 16) else f"-S{S}-G{G}") for n, d, S, G in rows]
+
+
+@pytest.mark.parametrize("name,dtype,S,G", _lean_rows()[0], ids=_lean_rows()[1])
+def test_lean_step_matches_general_step_on_the_same_draws(name, dtype, S, G):
     """FusedTrainer's launch-lean step (in-kernel draws, fused per-ray kernels, fold / unfold / Adam kernels; eager, then
     replayed from a HIP graph) against the general step (ATen glue; held to the autograd path and the
-    oracle by test_gpu_fuzz.py) fed with the Philox streams' draws as arrays: loss, rgb and parameters over five steps."""
+    oracle by test_gpu_fuzz.py) fed with the Philox streams' draws as arrays: loss, rgb and parameters over five steps.
+    R = 96 rays of S + G samples: R S is a tile multiple in both modes, so the lean step runs its merged form (two forward
+    launches into one set, one two-block backward); the (S, G) = (24, 8) rows run it with blocks of unequal sample counts."""
     import brdf_nerf_amd
     from test_gpu_parity import build_model, make_args, Replay, diag
     from brdf_nerf_amd import functions as Fn
     from brdf_nerf_amd.trainer import FusedTrainer
-    cfg = FieldConfig(feat=64, n_samples=16, guided_samples=16, **_lean_cfgs()[name])
+    cfg = FieldConfig(feat=64, n_samples=S, guided_samples=G, **_lean_cfgs()[name])
     args = make_args(cfg, dtype)
-    R, S, G = 96, 16, 16
+    R = 96
     g = torch.Generator().manual_seed(3)
     rays = _sat_rays(R, g).to(DEV)
     rgbs = torch.rand(R, 3, generator=g).to(DEV)
