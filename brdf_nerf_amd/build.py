@@ -62,15 +62,15 @@ def needs_build():
 # bytes of scratch per lane, the inference forward from 700 to 0 (profiles/history/r03_kernel_resources.txt).
 _NOSLP = ("-fno-slp-vectorize",)
 _TRACKERS = ("-mllvm", "-amdgpu-use-amdgpu-trackers=1") + _NOSLP
-# dsm.hip: the float64 point and cell chain must round operation by operation (a contracted multiply-add moves points across
-# cell boundaries); the file also carries the pragma.  metrics.hip: the SSIM tap sums and the normal chain are held to a float64
+# world.hip: the float64 point and cell chain of the DSM (surface_cell.h) and the geodesy it shares with camera.hip (geodesy.h)
+# must round operation by operation (a contracted multiply-add moves points across cell boundaries); the file also carries the
+# pragma.  metrics.hip: the SSIM tap sums and the normal chain are held to a float64
 # statement bit for bit, for the same reason; register.hip: the box means of the pyramid and the quanta of the altitudes likewise;
 # view_maps.hip: the serial float64 sums per ray and the shared normal chain likewise; camera.hip: the RPC polynomials and the Newton
-# steps of the localisation likewise; world.hip: the point and cell chain of dsm.hip and the geodesy it shares with camera.hip
-# (geodesy.h) likewise; ortho.hip: the same chain (surface_cell.h, shared with world.hip) and the quanta of the feature channels.
-FILE_FLAGS = {"field_wgrad.hip": ("-mllvm", "-amdgpu-sched-strategy=max-ilp"), "dsm.hip": ("-ffp-contract=off",),
+# steps of the localisation likewise; ortho.hip: world.hip's chain (surface_cell.h) and the quanta of the feature channels.
+FILE_FLAGS = {"field_wgrad.hip": ("-mllvm", "-amdgpu-sched-strategy=max-ilp"), "world.hip": ("-ffp-contract=off",),
               "metrics.hip": ("-ffp-contract=off",), "register.hip": ("-ffp-contract=off",), "view_maps.hip": ("-ffp-contract=off",),
-              "camera.hip": ("-ffp-contract=off",), "world.hip": ("-ffp-contract=off",), "ortho.hip": ("-ffp-contract=off",),
+              "camera.hip": ("-ffp-contract=off",), "ortho.hip": ("-ffp-contract=off",),
               "field_fwd.hip": _NOSLP,
               "field_bwd.hip": _TRACKERS, "field_adjoint.hip": _TRACKERS, "field_adjbwd.hip": _TRACKERS}
 

@@ -10,7 +10,7 @@
 // bn_normal_angle  the angle between two normal grids in degrees (calc_nr_diff, :164-173), a lane per cell, and integer
 //                  (sum, count) pairs over all / inside / outside cells: the nanmean of :341 and MaskDoD (:278-297, :346).
 //
-// As in dsm.hip every float64 operation is rounded on its own (the file is built with fp contraction off and carries the pragma):
+// As in world.hip every float64 operation is rounded on its own (the file is built with fp contraction off and carries the pragma):
 // the tests hold the maps to a numpy float64 statement bit for bit, and a fused multiply-add in a tap sum would round differently.
 // The sums are integer, so their bits do not depend on the block order or on how the rows are split over launches or devices;
 // there is no float atomic in this file.

@@ -13,16 +13,16 @@
 //                         walk the footprint together, so a wave's atomic instruction covers whole cells of 8 (2 + E) contiguous
 //                         bytes instead of one 8-byte word per cell.  The lanes of a ray read top[cell] at one address, which the
 //                         wave's load merges into one request.
-//                         -DBN_ORTHO_LANE_PER_RAY builds the plain form instead (a lane per ray issues the 2 + E atomics of a cell
-//                         one after the other): the same integers in another order, so not a bit can differ.
+//                         The plain form (a lane per ray issues the 2 + E atomics of a cell one after the other) gave the same
+//                         integers in another order and was retired; profiles/ortho_throughput.txt records the comparison.
 //   ortho_resolve_kernel  one lane per cell: the means
 //
 // Integer atomics only (add and signed max): every output bit depends on the set of rays alone.  Each counter is summed per block
 // in LDS and goes out as ONE integer atomic per block.
-// As the compiler reports them for gfx950: ortho_top_kernel 62 VGPRs and 4 B of LDS, ortho_splat_kernel 63 VGPRs and 1296 B of LDS
-// (the lane-per-ray form: 64 VGPRs, 12 B), ortho_resolve_kernel 18 VGPRs; none uses scratch, all run 8 waves per SIMD.  Timed
-// alternately in one process (profiles/ortho_throughput.txt; 512 x 512 view, 1.3 M deposits), the pair form takes 0.089 ms at E = 3
-// and 0.287 ms at E = 28 against 0.288 and 1.760 ms of the lane-per-ray form, and is the one kept.
+// As the compiler reports them for gfx950: ortho_top_kernel 62 VGPRs and 4 B of LDS, ortho_splat_kernel 63 VGPRs and 1296 B of LDS,
+// ortho_resolve_kernel 22 VGPRs and no LDS; none uses scratch, all run 8 waves per SIMD.  Timed alternately in one process
+// (profiles/ortho_throughput.txt; 512 x 512 view, 1.3 M deposits), the pair form takes 0.089 ms at E = 3 and 0.287 ms at E = 28
+// against 0.288 and 1.760 ms of the retired lane-per-ray form.
 #include <cmath>
 #include "common.h"
 #include "brdfnerf_hip.h"
@@ -76,7 +76,6 @@ void ortho_top_kernel(const PointArgs A, const ToEnz T, const GridArgs G, long l
   count_block(bad, skipped);
 }
 
-#ifndef BN_ORTHO_LANE_PER_RAY
 __global__ __launch_bounds__(ORTHO_BLOCK)
 void ortho_splat_kernel(const PointArgs A, const ToEnz T, const GridArgs G, const FeatureArgs F, unsigned long long *__restrict__ acc,
                         unsigned long long *__restrict__ counters) {
@@ -131,50 +130,6 @@ void ortho_splat_kernel(const PointArgs A, const ToEnz T, const GridArgs G, cons
   __syncthreads();
   if (tid < 3 && s_count[tid]) atomicAdd(counters + tid, (unsigned long long)s_count[tid]);
 }
-constexpr int ORTHO_SPLAT_RAYS = ORTHO_RAYS;
-#else
-// the plain form: a lane per ray
-__global__ __launch_bounds__(ORTHO_BLOCK)
-void ortho_splat_kernel(const PointArgs A, const ToEnz T, const GridArgs G, const FeatureArgs F, unsigned long long *__restrict__ acc,
-                        unsigned long long *__restrict__ counters) {
-  __shared__ unsigned int s_count[3];
-  const int tid = threadIdx.x;
-  const int64_t ray = (int64_t)blockIdx.x * ORTHO_BLOCK + tid;
-  if (tid < 3) s_count[tid] = 0;
-  __syncthreads();
-  unsigned int n_culled = 0;
-  if (ray < A.R) {
-    double e, n, a;
-    surface_point(A, T, ray, e, n, a);
-    int i, j;
-    long long q;
-    const int what = point_cell(G, e, n, a, i, j, q);
-    const float *x = F.x + ray * F.stride;
-    bool bad_x = false;
-    if (what != POINT_SKIPPED)
-      for (int k = 0; k < F.E; ++k) bad_x = bad_x || bad_feature(x[k]);
-    if (what == POINT_SKIPPED) atomicAdd(&s_count[0], 1u);
-    else if (bad_x) atomicAdd(&s_count[1], 1u);
-    else if (what == POINT_DEPOSIT) {
-      const int S = 2 + F.E;
-      for_footprint(G, i, j, [&](int64_t c) {
-        if (culled(F, q, c)) {
-          ++n_culled;
-          return;
-        }
-        unsigned long long *cell = acc + c * S;
-        atomicAdd(cell, (unsigned long long)q);
-        atomicAdd(cell + 1, 1ull);
-        for (int k = 0; k < F.E; ++k) atomicAdd(cell + 2 + k, (unsigned long long)feature_q(x[k]));
-      });
-    }
-  }
-  if (n_culled) atomicAdd(&s_count[2], n_culled);
-  __syncthreads();
-  if (tid < 3 && s_count[tid]) atomicAdd(counters + tid, (unsigned long long)s_count[tid]);
-}
-constexpr int ORTHO_SPLAT_RAYS = ORTHO_BLOCK;
-#endif
 
 __global__ __launch_bounds__(ORTHO_BLOCK)
 void ortho_resolve_kernel(const long long *__restrict__ acc, int64_t n, int32_t E, float *__restrict__ maps, float *__restrict__ dsm,
@@ -183,11 +138,9 @@ void ortho_resolve_kernel(const long long *__restrict__ acc, int64_t n, int32_t 
   if (c >= n) return;
   const long long *cell = acc + c * (2 + E);
   const long long cnt = cell[1];
-  const double dc = (double)cnt;
-  dsm[c] = cnt == 0 ? __builtin_nanf("") : (float)((double)cell[0] / dc * (1.0 / DSM_FIX));
-  if (count) count[c] = cnt > 0x7fffffffLL ? 0x7fffffff : (int32_t)cnt;
-  for (int e = 0; e < E; ++e)
-    maps[(int64_t)e * n + c] = cnt == 0 ? __builtin_nanf("") : (float)((double)cell[2 + e] / dc * (1.0 / ORTHO_FIX));
+  dsm[c] = cell_mean(cell[0], cnt, DSM_FIX);
+  if (count) count[c] = cell_count(cnt);
+  for (int e = 0; e < E; ++e) maps[(int64_t)e * n + c] = cell_mean(cell[2 + e], cnt, ORTHO_FIX);
 }
 
 }  // namespace
@@ -196,14 +149,12 @@ extern "C" int bn_ortho_top(const float *rays, int64_t ray_stride, const float *
                             double xoff, double yoff, double resolution, int32_t W, int32_t H, int32_t radius, int32_t footprint,
                             int32_t cs, int32_t zone, int32_t south, long long *top, unsigned long long *skipped, void *stream) {
   BN_REQUIRE(rays && depth && center && top && skipped, "ortho_top: null argument");
-  WORLD_REQUIRE_FRAME("ortho_top");
-  WORLD_REQUIRE_CELLS("ortho_top");
-  WORLD_REQUIRE_CS("ortho_top");
+  if (int bad = require_rays("ortho_top", R, ray_stride, center, range, cs, zone, south)) return bad;
+  if (int bad = require_cells("ortho_top", xoff, yoff, resolution, W, H, radius, footprint)) return bad;      // (top: 8-byte words)
   if (R == 0) return 0;
-  const PointArgs a{rays, depth, ray_stride, R, center[0], center[1], center[2], range};
-  const GridArgs g{xoff, yoff, resolution, W, H, radius, footprint == BN_DSM_DISC};
-  ortho_top_kernel<<<(unsigned)ceil_div64(R, ORTHO_BLOCK), ORTHO_BLOCK, 0, (hipStream_t)stream>>>(a, make_to_enz(cs, zone, south), g, top,
-                                                                                                skipped);
+  ortho_top_kernel<<<(unsigned)ceil_div64(R, ORTHO_BLOCK), ORTHO_BLOCK, 0, (hipStream_t)stream>>>(
+      make_point_args(rays, ray_stride, depth, R, center, range), make_to_enz(cs, zone, south),
+      make_grid_args(xoff, yoff, resolution, W, H, radius, footprint), top, skipped);
   BN_LAUNCH_CHECK("ortho_top");
   return 0;
 }
@@ -217,17 +168,15 @@ extern "C" int bn_ortho_splat(const float *rays, int64_t ray_stride, const float
   BN_REQUIRE(E == 0 || features, "ortho_splat: E=%d channels without features", E);
   BN_REQUIRE(feature_stride >= E, "ortho_splat: feature rows of %lld floats hold no %d channels", (long long)feature_stride, E);
   BN_REQUIRE(band_q >= 0, "ortho_splat: band_q=%lld is negative", band_q);
-  WORLD_REQUIRE_FRAME("ortho_splat");
-  WORLD_REQUIRE_GRID("ortho_splat");
-  WORLD_REQUIRE_CS("ortho_splat");
-  BN_REQUIRE(R <= (int64_t)ORTHO_SPLAT_RAYS * 0x7fffffff, "ortho_splat: R=%lld too large", (long long)R);
+  if (int bad = require_rays("ortho_splat", R, ray_stride, center, range, cs, zone, south)) return bad;
+  if (int bad = require_grid("ortho_splat", acc, xoff, yoff, resolution, W, H, radius, footprint)) return bad;
+  BN_REQUIRE(R <= (int64_t)ORTHO_RAYS * 0x7fffffff, "ortho_splat: R=%lld too large", (long long)R);
   if (R == 0) return 0;
-  const PointArgs a{rays, depth, ray_stride, R, center[0], center[1], center[2], range};
-  const GridArgs g{xoff, yoff, resolution, W, H, radius, footprint == BN_DSM_DISC};
   // |q| <= 2^43: a band of 2^44 or more already keeps everything, and q + band_q must not overflow
   const FeatureArgs f{features, feature_stride, E, top, band_q > ORTHO_BAND_MAX ? ORTHO_BAND_MAX : band_q};
-  ortho_splat_kernel<<<(unsigned)ceil_div64(R, ORTHO_SPLAT_RAYS), ORTHO_BLOCK, 0, (hipStream_t)stream>>>(
-      a, make_to_enz(cs, zone, south), g, f, reinterpret_cast<unsigned long long *>(acc), counters);
+  ortho_splat_kernel<<<(unsigned)ceil_div64(R, ORTHO_RAYS), ORTHO_BLOCK, 0, (hipStream_t)stream>>>(
+      make_point_args(rays, ray_stride, depth, R, center, range), make_to_enz(cs, zone, south),
+      make_grid_args(xoff, yoff, resolution, W, H, radius, footprint), f, reinterpret_cast<unsigned long long *>(acc), counters);
   BN_LAUNCH_CHECK("ortho_splat");
   return 0;
 }

@@ -1,5 +1,5 @@
 // The xy registration of a DSM on its ground truth (dsmr.compute_shift(scaling=False) / apply_shift as sat_utils.py:239-246 call
-// them) on the device: the step of the evaluation's line (eval.py:467-479) between the rasteriser of dsm.hip and the MAEs.
+// them) on the device: the step of the evaluation's line (eval.py:467-479) between the rasteriser of world.hip and the MAEs.
 //
 // bn_grid_halve      one level of dsmr.downsample2x: the mean of the finite cells of a 2 x 2 box, float64, a lane per output cell.
 // bn_ncc_moments     the six INTEGER moments (N, Su, Sv, Suu, Svv, Suv) of the valid pairs u[j][i], v[j + dy][i + dx] for every
@@ -8,7 +8,7 @@
 // bn_dsm_shift_diff  dsmr.apply_shift_ and the float32 difference of sat_utils.py:246 per cell, and integer (sum, count) pairs of
 //                    |diff| over all / inside / outside cells (the nanmean of :340 and MaskDoD, :344-345).
 //
-// As in dsm.hip and metrics.hip every float64 operation is rounded on its own (the build passes -ffp-contract=off for this file
+// As in world.hip and metrics.hip every float64 operation is rounded on its own (the build passes -ffp-contract=off for this file
 // and it carries the pragma) and every sum is an integer: the results' bits do not depend on the block order, on how the rows
 // are split over launches or on how many devices shared the grid.  There is no float atomic in this file.
 //

@@ -139,14 +139,26 @@ class Grid:
         return f"Grid(xoff={self.xoff}, yoff={self.yoff}, resolution={self.resolution}, width={self.width}, height={self.height})"
 
 
+def _rows_f32(rays, depth):
+    """A chunk as the splat entries take it: the rays and the flattened depth, float32 unless they already are."""
+    depth = depth.reshape(-1)
+    return (rays if rays.dtype == torch.float32 else rays.float()), (depth if depth.dtype == torch.float32 else depth.float())
+
+
+def _check_footprint(who, radius, footprint):
+    if footprint not in _FOOTPRINTS:
+        raise ValueError(f"{who}: footprint {footprint!r} ('disc' or 'square')")
+    if not 0 <= int(radius) <= L.BN_DSM_MAX_RADIUS:
+        raise ValueError(f"{who}: radius {radius} outside [0, {L.BN_DSM_MAX_RADIUS}]")
+
+
 def _ecef_points(rays, depth, frame, what):
     """bn_surface_points of an 'ecef' frame: float64 (R, 3) = (east, north, altitude), NaN where a row is refused."""
     if not rays.is_cuda:
         raise ValueError(f"{what}: the world points of an 'ecef' frame are converted on the device; the rays are on {rays.device}")
-    code, zone, south = frame.world_args()
-    depth = depth.reshape(-1).to(rays.device)
-    return Fn.surface_points(rays if rays.dtype == torch.float32 else rays.float(), depth if depth.dtype == torch.float32 else depth.float(),
-                             frame.center, frame.range, code, zone, south, torch.zeros((1,), dtype=torch.int64, device=rays.device))
+    rays, depth = _rows_f32(rays, depth.to(rays.device))
+    return Fn.surface_points(rays, depth, frame.center, frame.range, *frame.world_args(),
+                             torch.zeros((1,), dtype=torch.int64, device=rays.device))
 
 
 @torch.no_grad()
@@ -192,10 +204,7 @@ class DsmAccumulator:
     'square'.  Integer sums: the accumulator's bits depend on the set of rays alone."""
 
     def __init__(self, grid, device, radius=1, footprint="disc"):
-        if footprint not in _FOOTPRINTS:
-            raise ValueError(f"DsmAccumulator: footprint {footprint!r} ('disc' or 'square')")
-        if not 0 <= int(radius) <= L.BN_DSM_MAX_RADIUS:
-            raise ValueError(f"DsmAccumulator: radius {radius} outside [0, {L.BN_DSM_MAX_RADIUS}]")
+        _check_footprint("DsmAccumulator", radius, footprint)
         self.grid, self.radius, self.footprint = grid, int(radius), footprint
         self.acc = torch.zeros((grid.height, grid.width, 2), dtype=torch.int64, device=device)
         self._skipped = torch.zeros((1,), dtype=torch.int64, device=device)
@@ -203,8 +212,7 @@ class DsmAccumulator:
     @torch.no_grad()
     def add(self, rays, depth, frame):
         g = self.grid
-        depth = depth.reshape(-1)
-        rays, depth = rays if rays.dtype == torch.float32 else rays.float(), depth if depth.dtype == torch.float32 else depth.float()
+        rays, depth = _rows_f32(rays, depth)
         if frame.cs == "ecef":
             Fn.dsm_splat_world(rays, depth, frame.center, frame.range, g.xoff, g.yoff, g.resolution, self.radius,
                                _FOOTPRINTS[self.footprint], *frame.world_args(), self.acc, self._skipped)

@@ -731,20 +731,14 @@ def dsm_splat(rays, depth, center, rng, xoff, yoff, resolution, radius, footprin
     """The depths of R rays splatted into a DSM accumulator (bn_dsm_splat).  rays (R, >= 6) float32 rows with unit inner stride
     (origin, direction), depth (R,) float32; center (3 floats) and rng the scene normalisation, (xoff, yoff) the grid's north-west
     corner; acc (H, W, 2) int64 = (sum, count) and skipped (1,) int64 on the device, accumulated into."""
-    R = rays.shape[0]
-    assert rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] >= 6
-    assert depth.is_cuda and depth.dtype == torch.float32 and depth.shape == (R,)
-    assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] == 2 and acc.is_contiguous()
-    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    rays, depth, R, stride = _ray_rows(rays, depth)
+    H, W = _dsm_acc(acc, skipped)
     if R == 0:
         return acc
-    if rays.stride(1) != 1:
-        rays = rays.contiguous()
-    c = (C.c_double * 3)(*[float(v) for v in center])
-    H, W = acc.shape[0], acc.shape[1]
-    L.check(L.lib().bn_dsm_splat(C.c_void_p(rays.data_ptr()), rays.stride(0), _p(depth.contiguous()), R, c, float(rng), float(xoff),
-                                 float(yoff), float(resolution), W, H, int(radius), int(footprint), _p(acc), _p(skipped), _stream()),
-            "bn_dsm_splat")
+    with torch.cuda.device(rays.device):
+        L.check(L.lib().bn_dsm_splat(C.c_void_p(rays.data_ptr()), stride, _p(depth), R,
+                                     *_abi_args((center, rng), (xoff, yoff, resolution, W, H, radius, footprint)), _p(acc), _p(skipped),
+                                     _stream()), "bn_dsm_splat")
     return acc
 
 
@@ -756,17 +750,28 @@ def _ray_rows(rays, depth):
     return rays, depth.contiguous(), R, (rays.stride(0) if R > 1 else rays.shape[1])       # (one row: its stride is not read)
 
 
+def _counter(t, n=1):
+    assert t.is_cuda and t.dtype == torch.int64 and t.numel() == n and t.is_contiguous()
+
+
 def _dsm_acc(acc, skipped):
     assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] == 2 and acc.is_contiguous()
-    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    _counter(skipped)
     return acc.shape[0], acc.shape[1]
+
+
+def _abi_args(frame=(), grid=(), world=()):
+    """The arguments the surface-model entries share, in ABI order: frame (center, rng) -> center[3], range; grid (xoff, yoff,
+    resolution, W, H, radius, footprint); world (cs, zone, south).  An entry passes the parts it takes."""
+    frame = ((C.c_double * 3)(*[float(v) for v in frame[0]]), float(frame[1])) if frame else ()
+    return frame + tuple(float(v) for v in grid[:3]) + tuple(int(v) for v in grid[3:]) + tuple(int(v) for v in world)
 
 
 def ecef_geodetic(xyz, skipped):
     """Geodetic points of ECEF points (bn_ecef_geodetic): xyz (n, 3) float64 -> lonlat (n, 2) in degrees, alt (n,) float64, NaN
     where a point is refused (on the axis or not finite); skipped (1,) int64 on the device, accumulated into."""
     assert xyz.is_cuda and xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.shape[1] == 3
-    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    _counter(skipped)
     xyz = xyz.contiguous()
     n = xyz.shape[0]
     lonlat = torch.empty((n, 2), dtype=torch.float64, device=xyz.device)
@@ -783,14 +788,14 @@ def surface_points(rays, depth, center, rng, cs, zone, south, skipped):
     depth (R,) float32; cs BN_CS_ECEF or BN_CS_UTM, the scene's zone -> float64 (R, 3), NaN where a row is refused; skipped (1,)
     int64 on the device, accumulated into."""
     rays, depth, R, stride = _ray_rows(rays, depth)
-    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    _counter(skipped)
     enz = torch.empty((R, 3), dtype=torch.float64, device=rays.device)
     if R == 0:
         return enz
-    c = (C.c_double * 3)(*[float(v) for v in center])
     with torch.cuda.device(rays.device):
-        L.check(L.lib().bn_surface_points(C.c_void_p(rays.data_ptr()), stride, _p(depth), R, c, float(rng), int(cs), int(zone),
-                                          int(south), _p(enz), _p(skipped), _stream()), "bn_surface_points")
+        L.check(L.lib().bn_surface_points(C.c_void_p(rays.data_ptr()), stride, _p(depth), R,
+                                          *_abi_args((center, rng), world=(cs, zone, south)), _p(enz), _p(skipped), _stream()),
+                "bn_surface_points")
     return enz
 
 
@@ -805,8 +810,8 @@ def dsm_splat_points(enz, xoff, yoff, resolution, radius, footprint, acc, skippe
         enz = enz.contiguous()
     with torch.cuda.device(enz.device):
         L.check(L.lib().bn_dsm_splat_points(C.c_void_p(enz.data_ptr()), enz.stride(0) if enz.shape[0] > 1 else enz.shape[1], enz.shape[0],
-                                            float(xoff), float(yoff), float(resolution), W, H, int(radius), int(footprint), _p(acc),
-                                            _p(skipped), _stream()), "bn_dsm_splat_points")
+                                            *_abi_args(grid=(xoff, yoff, resolution, W, H, radius, footprint)), _p(acc), _p(skipped),
+                                            _stream()), "bn_dsm_splat_points")
     return acc
 
 
@@ -817,18 +822,11 @@ def dsm_splat_world(rays, depth, center, rng, xoff, yoff, resolution, radius, fo
     H, W = _dsm_acc(acc, skipped)
     if R == 0:
         return acc
-    c = (C.c_double * 3)(*[float(v) for v in center])
     with torch.cuda.device(rays.device):
-        L.check(L.lib().bn_dsm_splat_world(C.c_void_p(rays.data_ptr()), stride, _p(depth), R, c, float(rng), float(xoff),
-                                           float(yoff), float(resolution), W, H, int(radius), int(footprint), int(cs), int(zone),
-                                           int(south), _p(acc), _p(skipped), _stream()), "bn_dsm_splat_world")
+        L.check(L.lib().bn_dsm_splat_world(C.c_void_p(rays.data_ptr()), stride, _p(depth), R,
+                                           *_abi_args((center, rng), (xoff, yoff, resolution, W, H, radius, footprint), (cs, zone, south)),
+                                           _p(acc), _p(skipped), _stream()), "bn_dsm_splat_world")
     return acc
-
-
-def _ortho_grid(args, cs, zone, south):
-    center, rng, xoff, yoff, resolution, radius, footprint = args
-    return ((C.c_double * 3)(*[float(v) for v in center]), float(rng), float(xoff), float(yoff), float(resolution)), \
-        (int(radius), int(footprint), int(cs), int(zone), int(south))
 
 
 def ortho_top(rays, depth, center, rng, xoff, yoff, resolution, radius, footprint, cs, zone, south, top, skipped):
@@ -837,13 +835,13 @@ def ortho_top(rays, depth, center, rng, xoff, yoff, resolution, radius, footprin
     (1,) int64 on the device, accumulated into."""
     rays, depth, R, stride = _ray_rows(rays, depth)
     assert top.is_cuda and top.dtype == torch.int64 and top.dim() == 2 and top.is_contiguous()
-    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    _counter(skipped)
     if R == 0:
         return top
     H, W = top.shape
-    (c, rng, xoff, yoff, resolution), tail = _ortho_grid((center, rng, xoff, yoff, resolution, radius, footprint), cs, zone, south)
     with torch.cuda.device(rays.device):
-        L.check(L.lib().bn_ortho_top(C.c_void_p(rays.data_ptr()), stride, _p(depth), R, c, rng, xoff, yoff, resolution, W, H, *tail,
+        L.check(L.lib().bn_ortho_top(C.c_void_p(rays.data_ptr()), stride, _p(depth), R,
+                                     *_abi_args((center, rng), (xoff, yoff, resolution, W, H, radius, footprint), (cs, zone, south)),
                                      _p(top), _p(skipped), _stream()), "bn_ortho_top")
     return top
 
@@ -857,7 +855,7 @@ def ortho_splat(rays, depth, center, rng, xoff, yoff, resolution, radius, footpr
     rays, depth, R, stride = _ray_rows(rays, depth)
     assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] >= 2 and acc.is_contiguous()
     H, W, E = acc.shape[0], acc.shape[1], acc.shape[2] - 2
-    assert counters.is_cuda and counters.dtype == torch.int64 and counters.numel() == 3 and counters.is_contiguous()
+    _counter(counters, 3)
     assert top is None or (top.is_cuda and top.dtype == torch.int64 and top.shape == (H, W) and top.is_contiguous())
     if E == 0:
         assert features is None or (features.dim() == 2 and features.shape == (R, 0))
@@ -869,9 +867,9 @@ def ortho_splat(rays, depth, center, rng, xoff, yoff, resolution, radius, footpr
         fp, fs = C.c_void_p(features.data_ptr()), (features.stride(0) if R > 1 else E)       # (one row: its stride is not read)
     if R == 0:
         return acc
-    (c, rng, xoff, yoff, resolution), tail = _ortho_grid((center, rng, xoff, yoff, resolution, radius, footprint), cs, zone, south)
     with torch.cuda.device(rays.device):
-        L.check(L.lib().bn_ortho_splat(C.c_void_p(rays.data_ptr()), stride, _p(depth), R, c, rng, xoff, yoff, resolution, W, H, *tail,
+        L.check(L.lib().bn_ortho_splat(C.c_void_p(rays.data_ptr()), stride, _p(depth), R,
+                                       *_abi_args((center, rng), (xoff, yoff, resolution, W, H, radius, footprint), (cs, zone, south)),
                                        fp, fs, E, _p(top), int(band_q), _p(acc), _p(counters), _stream()), "bn_ortho_splat")
     return acc
 
@@ -896,7 +894,8 @@ def dsm_resolve(acc, want_count=True):
     H, W = acc.shape[0], acc.shape[1]
     dsm = torch.empty((H, W), dtype=torch.float32, device=acc.device)
     count = torch.empty((H, W), dtype=torch.int32, device=acc.device) if want_count else None
-    L.check(L.lib().bn_dsm_resolve(_p(acc), W, H, _p(dsm), _p(count), _stream()), "bn_dsm_resolve")
+    with torch.cuda.device(acc.device):
+        L.check(L.lib().bn_dsm_resolve(_p(acc), W, H, _p(dsm), _p(count), _stream()), "bn_dsm_resolve")
     return dsm, count
 
 

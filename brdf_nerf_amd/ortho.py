@@ -28,7 +28,7 @@ import torch
 
 from . import _lib as L
 from . import functions as Fn
-from .dsm import _FOOTPRINTS, _cloud_grid
+from .dsm import _FOOTPRINTS, _check_footprint, _cloud_grid, _rows_f32
 
 _MODES = ("top", "mean")
 BAND_FIX = 2.0 ** 20
@@ -61,10 +61,7 @@ class OrthoAccumulator:
     DsmAccumulator's, bit for bit."""
 
     def __init__(self, grid, device, channels, radius=1, footprint="disc", mode="top", band=0.5):
-        if footprint not in _FOOTPRINTS:
-            raise ValueError(f"OrthoAccumulator: footprint {footprint!r} ('disc' or 'square')")
-        if not 0 <= int(radius) <= L.BN_DSM_MAX_RADIUS:
-            raise ValueError(f"OrthoAccumulator: radius {radius} outside [0, {L.BN_DSM_MAX_RADIUS}]")
+        _check_footprint("OrthoAccumulator", radius, footprint)
         if mode not in _MODES:
             raise ValueError(f"OrthoAccumulator: unknown mode {mode!r} ('top' or 'mean')")
         if not 0 <= int(channels) <= L.BN_ORTHO_MAX_CHANNELS:
@@ -82,18 +79,13 @@ class OrthoAccumulator:
         g = self.grid
         return (frame.center, frame.range, g.xoff, g.yoff, g.resolution, self.radius, _FOOTPRINTS[self.footprint]) + frame.world_args()
 
-    @staticmethod
-    def _rows(rays, depth):
-        depth = depth.reshape(-1)
-        return (rays if rays.dtype == torch.float32 else rays.float()), (depth if depth.dtype == torch.float32 else depth.float())
-
     @torch.no_grad()
     def add_top(self, rays, depth, frame):
         if self.mode != "top":
             raise ValueError("OrthoAccumulator.add_top: mode='mean' has no top-surface pass")
         if self._added:
             raise ValueError("OrthoAccumulator.add_top: pass 1 must have seen every ray before pass 2 starts, and add() has been called")
-        rays, depth = self._rows(rays, depth)
+        rays, depth = _rows_f32(rays, depth)
         Fn.ortho_top(rays, depth, *self._args(frame), self.top, self._top_skipped)
         return self
 
@@ -112,7 +104,7 @@ class OrthoAccumulator:
         if not given and not (E == 0 and features is None):
             what = f"{tuple(features.shape)} {features.dtype} on {features.device}" if torch.is_tensor(features) else repr(type(features))
             raise ValueError(f"OrthoAccumulator.add: features must be ({R}, {E}) float32 on the device, got {what}")
-        rays, depth = self._rows(rays, depth)
+        rays, depth = _rows_f32(rays, depth)
         self._added = True
         Fn.ortho_splat(rays, depth, *self._args(frame), features if E else None, self.top, self.band_q, self.acc, self._counters)
         return self

@@ -1,10 +1,9 @@
-"""Orthorectified maps: what the two passes and the resolve cost, and which lane mapping of the splat is the faster one.  A
+"""Orthorectified maps: what the two passes and the resolve cost.  A
 512 x 512 synthetic view (262,144 rays), RPV111 + analytic normals, bf16, 0.5 m cells, radius 1 (disc), range 128 m (the view at
 its own ground sampling distance), E = 3 and E = 28 random feature channels, mean and top mode (band 0.5 m).
 
-(a) by device events, the runs of the two libraries ALTERNATING in one process: bn_ortho_top, bn_ortho_splat and bn_ortho_resolve
-    of the in-tree library (lanes own (ray, slot) pairs) against the -DBN_ORTHO_LANE_PER_RAY build (a lane per ray), when that
-    variant has been built:  python -m brdf_nerf_amd.build -DBN_ORTHO_LANE_PER_RAY --tag=ortho_lane_per_ray
+(a) by device events: bn_ortho_top, bn_ortho_splat and bn_ortho_resolve (the recorded
+    profiles/ortho_throughput.txt also holds the retired lane-per-ray form of the splat, which this script no longer builds)
     and the same rasterisation as float64 index_put_(accumulate=True) in torch; all rays on a 25 x 27 grid as the contention case;
 (b) as whole calls by a host clock: ortho_image against view_maps.
 Ends with bench.py in a child process as the box-speed indicator of the visit.  Writes profiles/ortho_throughput.txt (or the path
@@ -19,34 +18,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "profiles"))
 import torch  # noqa: E402
 import bench  # noqa: E402
-from dsm_throughput import LINES, say, timed  # noqa: E402
+from dsm_throughput import LINES, device_ms, say, timed  # noqa: E402
 from brdf_nerf_amd import Grid, OrthoAccumulator, SceneFrame, load_model, ortho_image, point_cloud, view_maps  # noqa: E402
-from brdf_nerf_amd import _lib as L  # noqa: E402
 from brdf_nerf_amd import functions as Fn  # noqa: E402
 from brdf_nerf_amd.dsm import _cloud_grid  # noqa: E402
 from brdf_nerf_amd.evaluate import render_image  # noqa: E402
-
-VARIANT = os.environ.get("BRDFNERF_ORTHO_VARIANT") or os.path.join(ROOT, "brdf_nerf_amd", "build", "ortho_lane_per_ray", "libbrdfnerf_hip.so")
-
-
-def alternate(fns, rounds=5, reps=4):
-    """fns: {name: (library handle, callable)}.  Round by round, every callable in turn under its library, `reps` device-event
-    timings each (round 0 is the warm-up) -> {name: (min ms, median ms)}."""
-    ts = {k: [] for k in fns}
-    for rnd in range(rounds + 1):
-        for name, (handle, fn) in fns.items():
-            L.use(handle)
-            fn()
-            torch.cuda.synchronize()
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-            for a, b in ev:
-                a.record()
-                fn()
-                b.record()
-            torch.cuda.synchronize()
-            if rnd:
-                ts[name] += [a.elapsed_time(b) for a, b in ev]
-    return {k: (min(v), sorted(v)[len(v) // 2]) for k, v in ts.items()}
 
 
 def torch_rasteriser(rays, depth, features, frame, grid, radius=1):
@@ -87,13 +63,6 @@ def measure():
     flags = dict(bench.CONFIG_FLAGS[config][1])
     say(f"view 512 x 512 = {N} rays, {config} {dtype}, S = G = 64, chunk {chunk}; 0.5 m cells, radius 1 (disc), range 128 m, band 0.5 m; "
         f"device {torch.cuda.get_device_name(0)}")
-    tree = L.lib()
-    libs = {"pairs": tree}
-    if os.path.exists(VARIANT):
-        libs["lane per ray"] = L.load(VARIANT)
-        say(f"variant library: {os.path.relpath(VARIANT, ROOT)} (build flags {libs['lane per ray'].bn_build_flags().decode()!r})")
-    else:
-        say("variant library not built: the lane-per-ray mapping was NOT measured")
     frame = SceneFrame((368412.25, 3359871.75, 12.5), 128.0)
     with torch.no_grad():
         torch.manual_seed(1)
@@ -111,20 +80,19 @@ def measure():
                     acc = OrthoAccumulator(grid, dev, E, mode=mode, band=0.5)
                     if mode == "top":
                         acc.add_top(rays, depth, frame)
-                    zero_ms = alternate({"zero": (tree, lambda: acc.acc.zero_())}, 2)["zero"][0]
+                    zero_ms = device_ms(lambda: acc.acc.zero_())[0]
 
                     def splat():
                         acc.acc.zero_()
                         acc.add(rays, depth, frame, feats)
-                    fns = {f"splat, {k}": (h, splat) for k, h in libs.items()}
+                    fns = {"splat": splat}
                     if mode == "top":
                         # (a max is idempotent: no refill needed; the entry itself, since add_top is refused once add has run)
-                        fns["top"] = (tree, lambda: Fn.ortho_top(rays, depth, *acc._args(frame), acc.top, acc._top_skipped))
-                    fns["resolve"] = (tree, acc.result)
+                        fns["top"] = lambda: Fn.ortho_top(rays, depth, *acc._args(frame), acc.top, acc._top_skipped)
+                    fns["resolve"] = acc.result
                     if mode == "mean":
-                        fns["torch index_put_ float64"] = (tree, lambda: torch_rasteriser(rays, depth, feats, frame, grid))
-                    ts = alternate(fns)
-                    L.use(tree)
+                        fns["torch index_put_ float64"] = lambda: torch_rasteriser(rays, depth, feats, frame, grid)
+                    ts = {name: device_ms(fn) for name, fn in fns.items()}
                     acc._counters.zero_()
                     splat()
                     deposits, culled = int(acc.acc[..., 1].sum()), acc.culled
@@ -136,7 +104,6 @@ def measure():
                         gap = (torch_rasteriser(rays, depth, feats, frame, grid) - acc.result()[0].permute(1, 2, 0))
                         line += f"; max |torch - maps| {float(gap[torch.isfinite(gap)].abs().max()):.2e}"
                     say(line)
-        L.use(tree)
         H = W = side
         vm = view_maps(models, args, rays, H, W, chunk=chunk, **flags)["maps"]
         keys3, keys28, n = ("rgb",), [], 0

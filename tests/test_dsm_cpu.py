@@ -169,3 +169,24 @@ def test_accumulator_refuses_bad_arguments_before_any_device_work():
         DsmAccumulator(g, "cpu", radius=-1)
     with pytest.raises(ValueError, match="footprint"):
         DsmAccumulator(g, "cpu", footprint="gauss")
+
+
+def test_the_chain_is_stated_once():
+    """The point, cell and deposit chain has one statement, csrc/surface_cell.h, which world.hip (every DSM entry) and ortho.hip are
+    made of: no second copy of the arithmetic, of its argument struct or of the host checks as macros, and no retired A/B form."""
+    from brdf_nerf_amd.build import FILE_FLAGS
+    csrc = os.path.join(ROOT, "brdf_nerf_amd", "csrc")
+    assert not os.path.exists(os.path.join(csrc, "dsm.hip")) and "dsm.hip" not in FILE_FLAGS
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))}
+    hips = [f for f in text if f.endswith(".hip")]
+    assert "world.hip" in hips and "ortho.hip" in hips
+    cell_index = re.compile(r"floor\(\([^\n]*/[^\n]*resolution\)")
+    assert len(cell_index.findall(text["surface_cell.h"])) == 2          # the column and the row
+    for f in text:                                                       # (the headers too)
+        assert "struct DsmArgs" not in text[f] and "#define WORLD_REQUIRE_" not in text[f], f
+    for f in hips:
+        assert not cell_index.search(text[f]), f
+    assert '#include "surface_cell.h"' in text["world.hip"] and "#pragma clang fp contract(off)" in text["world.hip"]
+    assert "-ffp-contract=off" in FILE_FLAGS["world.hip"]
+    for f, s in text.items():
+        assert "BN_ORTHO_LANE_PER_RAY" not in s, f

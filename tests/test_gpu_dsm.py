@@ -163,3 +163,76 @@ def test_two_rank_dsm_matches_one_rank():
             outs.append("TIMEOUT\n" + p.communicate()[0])
     assert all(p.returncode == 0 for p in procs), "\n".join(outs)
     assert all("RESULT" in o and "ok" in o for o in outs), "\n".join(outs)
+
+
+def _block_edge_rows():
+    """257 rows on SMALL (radius 1, disc): rows 0, 63, 64, 255 and 256 - the first and last lane of a wave, the first lane of the
+    next, the last lane of a block and a block of one lane - must be skipped; every other row lands on the grid."""
+    k = np.arange(257)
+    rays, depth = D._nadir(-2.8125 + 0.1875 * (k % 17), -1.3125 + 0.1875 * (k % 13), -3.0 + 0.75 * (k % 7), 0.5)
+    depth[0] = np.nan                                            # NaN depth
+    rays[63, 0] = np.inf                                         # inf origin
+    rays[64, 2], rays[64, 5], depth[64] = 0.25, 1.0, 1398099.0   # altitude == 2^23 exactly (dsm_cases._bad_rows)
+    rays[255, 5], depth[255] = -1.0, 2.0e6                       # altitude about -1.2e7 m
+    rays[256, 1], depth[256] = -np.inf, np.nan                   # both
+    return rays, depth
+
+
+def test_block_edges_of_the_shared_kernel():
+    """bn_dsm_splat runs the kernel of bn_dsm_splat_world, which counts its skipped rows per block (no lane leaves early): bad rows
+    at a wave edge, a block edge and alone in a last block of one lane, then a bad row on its own (R = 1) and a whole block
+    (R = 256).  acc and skipped are the statement's integers exactly."""
+    from brdf_nerf_amd import _lib as L
+    from brdf_nerf_amd import functions as Fn
+    rays, depth = _block_edge_rows()
+    xoff, yoff, res, W, H = D.SMALL
+    for R, bad in ((257, 5), (1, 1), (256, 4)):
+        sums, counts, skipped = D.splat(rays[:R], depth[:R], D.SMALL, 1, "disc")
+        assert skipped == bad and int(D.splat(rays[:R], depth[:R], D.SMALL, 0, "disc")[1].sum()) == R - bad      # all others land
+        acc, sk = torch.zeros((H, W, 2), dtype=torch.int64, device=DEV), torch.zeros((1,), dtype=torch.int64, device=DEV)
+        Fn.dsm_splat(torch.from_numpy(rays[:R].copy()).to(DEV), torch.from_numpy(depth[:R].copy()).to(DEV), D.CENTER, D.RANGE, xoff, yoff,
+                     res, 1, L.BN_DSM_DISC, acc, sk)
+        got = acc.cpu().numpy()
+        print(f"R = {R}: cells with another sum {int((got[..., 0] != D.as_int64(sums)).sum())}, another count "
+              f"{int((got[..., 1] != D.as_int64(counts)).sum())}; skipped {int(sk)} (statement {skipped})")
+        assert np.array_equal(got[..., 0], D.as_int64(sums)) and np.array_equal(got[..., 1], D.as_int64(counts)), R
+        assert int(sk) == skipped, R
+
+
+def test_one_row_of_a_narrow_view():
+    """One row of a (1, 8) tensor expanded to (4, 8) has row stride 0, which is never read: rays[2:3] gives the accumulator of its
+    contiguous copy through bn_dsm_splat as through bn_dsm_splat_world."""
+    from brdf_nerf_amd import _lib as L
+    from brdf_nerf_amd import functions as Fn
+    row, t = D._one_point()
+    rays = torch.from_numpy(row.copy()).to(DEV).expand(4, 8)
+    depth = torch.from_numpy(t.copy()).to(DEV).expand(4).contiguous()
+    assert rays.stride(0) == 0 and rays[2:3].shape == (1, 8)
+    xoff, yoff, res, W, H = D.SMALL
+    grid = (D.CENTER, D.RANGE, xoff, yoff, res, 1, L.BN_DSM_DISC)
+    for name, splat in (("dsm_splat", lambda r, d, a, s: Fn.dsm_splat(r, d, *grid, a, s)),
+                        ("dsm_splat_world", lambda r, d, a, s: Fn.dsm_splat_world(r, d, *grid, L.BN_CS_UTM, 1, 0, a, s))):
+        got, want = (torch.zeros((H, W, 2), dtype=torch.int64, device=DEV) for _ in range(2))
+        sk = torch.zeros((1,), dtype=torch.int64, device=DEV)
+        splat(rays[2:3], depth[2:3], got, sk)
+        splat(rays[2:3].contiguous(), depth[2:3], want, sk)
+        assert int(want[..., 1].sum()) == 5 and int(sk) == 0, name
+        assert torch.equal(got, want), name
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs a second device")
+def test_a_device_that_is_not_the_current_one():
+    """bn_dsm_splat and bn_dsm_resolve launch on the stream of the tensors' device, whichever device is current."""
+    from brdf_nerf_amd import DsmAccumulator, Grid
+    name = "small_R65_r1_disc"
+    grid, radius, footprint, rays, depth = D.case(name)
+    want = D.expected(name)
+    other = torch.device("cuda", 1)
+    with torch.cuda.device(0):
+        acc = DsmAccumulator(Grid(*grid), other, radius=radius, footprint=footprint)
+        acc.add(torch.from_numpy(rays.copy()).to(other), torch.from_numpy(depth.copy()).to(other), frame())
+        dsm, count = acc.result()
+        torch.cuda.synchronize(other)
+    got = acc.acc.cpu().numpy()
+    assert np.array_equal(got[..., 0], want["sums"]) and np.array_equal(got[..., 1], want["counts"]) and acc.skipped == want["skipped"]
+    assert np.array_equal(dsm.cpu().numpy().view(np.int32), want["dsm"].view(np.int32)) and np.array_equal(count.cpu().numpy(), want["count"])
