@@ -69,6 +69,7 @@ BN_MAPS_MAX_SAMPLES, BN_MAPS_MAX_CHANNELS = 4096, 64
 BN_RPC_NEWTON_ITERS = 8
 BN_CS_ECEF, BN_CS_UTM = 0, 1
 BN_ORTHO_MAX_CHANNELS, BN_ORTHO_EMPTY = 32, -(1 << 63)
+BN_VIS_BLOCKED, BN_VIS_VISIBLE, BN_VIS_NODATA, BN_VIS_MAX_DIRS = 0, 1, 2, 4096
 
 
 class Rpc(C.Structure):               # bn_rpc: 90 doubles
@@ -186,6 +187,10 @@ _SIGS = {
                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fptr, C.c_int64, C.c_int32,
                                  fptr, C.c_longlong, fptr, fptr, fptr]),
     "bn_ortho_resolve": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_int32, fptr, fptr, fptr, fptr]),
+    "bn_grid_visibility": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32,
+                                     C.c_double, C.c_double, fptr, fptr, fptr, fptr]),
+    "bn_points_visibility": (C.c_int, [fptr, C.c_int64, fptr, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                       C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_double, fptr, fptr, fptr, fptr]),
     "bn_ssim_map": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, fptr, C.c_double,
                               C.c_double, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, fptr, fptr, fptr]),
     "bn_grid_normals": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_double, fptr, fptr]),

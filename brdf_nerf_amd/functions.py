@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the stream and stitches the 
 every numerical step of the hot path runs in the HIP library.  No CPU fallback exists.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -1045,6 +1046,112 @@ def grid_fill(src, near_row, rows=None, want_source=False, want_dist2=False):
     L.check(L.lib().bn_grid_fill(_p(src), _p(near_row), H, W, row0, row1, _p(dst), _p(source), _p(dist2), _p(counts), _stream()),
             "bn_grid_fill")
     return dst, source, dist2, counts
+
+
+def _vis_grid(name, dsm):
+    """The height grid of the visibility entries: (H, W) float32, contiguous, H W at most 2^30, or ValueError by name."""
+    if not isinstance(dsm, torch.Tensor):
+        raise ValueError(f"{name}: dsm must be a tensor on the device (there is no host path)")
+    if dsm.dtype != torch.float32:
+        raise ValueError(f"{name}: dsm is {dsm.dtype}, not torch.float32")
+    if dsm.dim() != 2 or not dsm.is_contiguous():
+        raise ValueError(f"{name}: dsm {tuple(dsm.shape)} is not a contiguous 2-D (H, W) grid")
+    if dsm.shape[0] < 1 or dsm.shape[1] < 1 or dsm.shape[0] * dsm.shape[1] > 1 << 30:
+        raise ValueError(f"{name}: dsm of {dsm.shape[0]} x {dsm.shape[1]} cells (H W from 1 to 2^30)")
+    return dsm
+
+
+def _vis_points(name, points):
+    """The starts of point mode: (R, 3) float64, R at most 2^30, or ValueError by name; the device is checked by _fill_device, last."""
+    if not isinstance(points, torch.Tensor):
+        raise ValueError(f"{name}: points must be a tensor on the device (there is no host path)")
+    if points.dtype != torch.float64:
+        raise ValueError(f"{name}: points are {points.dtype}, not torch.float64 (point_cloud's output)")
+    if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] > 1 << 30:
+        raise ValueError(f"{name}: points {tuple(points.shape)} are not (R, 3) with R at most 2^30")
+    return points
+
+
+def _vis_dirs(name, dirs):
+    """(K, 3) or (3,) directions in any float dtype -> (K, 3) float64 on the HOST (the entries check them there), K in
+    [1, BN_VIS_MAX_DIRS], every component finite and dz > 0, or ValueError by name."""
+    dirs = torch.as_tensor(dirs)
+    if not dirs.is_floating_point():
+        raise ValueError(f"{name}: dirs are {dirs.dtype}, not a float dtype")
+    dirs = dirs.detach().to(device="cpu", dtype=torch.float64)
+    if dirs.dim() == 1 and dirs.numel() == 3:
+        dirs = dirs.reshape(1, 3)
+    if dirs.dim() != 2 or dirs.shape[1] != 3 or not 1 <= dirs.shape[0] <= L.BN_VIS_MAX_DIRS:
+        raise ValueError(f"{name}: dirs {tuple(dirs.shape)} are not (K, 3) or (3,) with K from 1 to {L.BN_VIS_MAX_DIRS}")
+    if not bool(torch.isfinite(dirs).all()) or not bool((dirs[:, 2] > 0).all()):
+        raise ValueError(f"{name}: every direction must be finite and point above the horizon (dz > 0)")
+    return dirs.contiguous()
+
+
+def _vis_scalars(name, res, eps, zmax):
+    res, eps, zmax = float(res), float(eps), float(zmax)
+    if not (res > 0 and math.isfinite(res)):
+        raise ValueError(f"{name}: resolution {res} must be positive and finite")
+    if not (eps >= 0 and math.isfinite(eps)):
+        raise ValueError(f"{name}: eps {eps} must be finite and not negative")
+    if math.isnan(zmax):
+        raise ValueError(f"{name}: zmax is NaN")
+    return res, eps, zmax
+
+
+def grid_visibility(dsm, res, dirs, eps=0.0, zmax=float("inf"), rows=None, vis=None, hit=None, counts=None, want_hit=False):
+    """The visibility of the cells of a height grid (bn_grid_visibility): dsm (H, W) float32 on the device, dirs (K, 3) (east,
+    north, up) towards the sun or the sensor, taken to float64 on the host.  rows = (row0, row1): only those rows are written (the
+    others are uninitialised unless `vis` / `hit` come in) and counted.  vis (K, H, W) uint8, hit (K, H, W) int32 and counts (K, 3)
+    int64 may be given - counts are accumulated into.  -> vis, hit or None (want_hit, or `hit` given), counts."""
+    name = "grid_visibility"
+    _vis_grid(name, dsm)
+    dirs = _vis_dirs(name, dirs)
+    res, eps, zmax = _vis_scalars(name, res, eps, zmax)
+    H, W = dsm.shape
+    K = dirs.shape[0]
+    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= row0 <= row1 <= H:
+        raise ValueError(f"{name}: rows ({row0}, {row1}) outside [0, {H}]")
+    for t, dtype, shape, what in ((vis, torch.uint8, (K, H, W), "vis"), (hit, torch.int32, (K, H, W), "hit"), (counts, torch.int64, (K, 3), "counts")):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError(f"{name}: {what} must be a contiguous {dtype} tensor of shape {shape}")
+    _fill_device(name, dsm, *(t for t in (vis, hit, counts) if t is not None))
+    dev = dsm.device
+    if vis is None:
+        vis = torch.empty((K, H, W), dtype=torch.uint8, device=dev)
+    if hit is None and want_hit:
+        hit = torch.empty((K, H, W), dtype=torch.int32, device=dev)
+    if counts is None:
+        counts = torch.zeros((K, 3), dtype=torch.int64, device=dev)
+    L.check(L.lib().bn_grid_visibility(_p(dsm), H, W, res, row0, row1, dirs.numpy().ctypes.data_as(C.POINTER(C.c_double)), K, eps, zmax,
+                                       _p(vis), _p(hit), _p(counts), _stream()), "bn_grid_visibility")
+    return vis, hit, counts
+
+
+def points_visibility(points, dsm, xoff, yoff, res, dirs, eps=0.0, zmax=float("inf"), want_hit=False):
+    """The visibility of world points over a height grid (bn_points_visibility): points (R, 3) float64 (east, north, altitude) on
+    the device (point_cloud's output), dsm (H, W) float32 with its Grid's origin and resolution, dirs (K, 3).
+    -> vis (K, R) uint8, hit (K, R) int32 or None, counts (K, 3) int64."""
+    name = "points_visibility"
+    _vis_points(name, points)
+    _vis_grid(name, dsm)
+    dirs = _vis_dirs(name, dirs)
+    res, eps, zmax = _vis_scalars(name, res, eps, zmax)
+    xoff, yoff = float(xoff), float(yoff)
+    if not (math.isfinite(xoff) and math.isfinite(yoff)):
+        raise ValueError(f"{name}: grid origin ({xoff}, {yoff}) is not finite")
+    _fill_device(name, points, dsm)
+    points = points.contiguous()
+    H, W = dsm.shape
+    R, K = points.shape[0], dirs.shape[0]
+    vis = torch.empty((K, R), dtype=torch.uint8, device=dsm.device)
+    hit = torch.empty((K, R), dtype=torch.int32, device=dsm.device) if want_hit else None
+    counts = torch.zeros((K, 3), dtype=torch.int64, device=dsm.device)
+    if R:
+        L.check(L.lib().bn_points_visibility(_p(points), R, _p(dsm), H, W, xoff, yoff, res, dirs.numpy().ctypes.data_as(C.POINTER(C.c_double)),
+                                             K, eps, zmax, _p(vis), _p(hit), _p(counts), _stream()), "bn_points_visibility")
+    return vis, hit, counts
 
 
 RAY_MAP_COUNTERS = ("std_sum", "std_count", "std_skipped", "bad_nr", "nr0", "nr_total")

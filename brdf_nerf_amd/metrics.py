@@ -188,7 +188,8 @@ def normal_angle_mae(dsm, gt, resolution, mask=None, border="reference"):
 
 @torch.no_grad()
 def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=None, grid=None, dsm_mask=None, group=None,
-               window=3, layout="reference", radius=1, footprint="disc", resolution=0.5, register="z", **render_kw):
+               window=3, layout="reference", radius=1, footprint="disc", resolution=0.5, register="z", sun_dir=None, shadow_dsm=None,
+               shadow_eps=0.0, **render_kw):
     """The reference's evaluation line of one view (eval.py:467-479) in one call: psnr, psnr_scl, ssim, ssim_scl and - with a
     `frame` - the DSM, and with `gt_dsm` on that grid mae, mae_in, mae_out (altitude_mae) and mae_nr (normal_angle_mae).
     rays (H W, >= 8), rgbs (H W, 3) the ground truth, mask the view's valid pixels ((H, W) or (H W,)), dsm_mask the DSM's
@@ -200,6 +201,13 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
     register: 'z' - the z-only registration the reference falls back to without dsmr (altitude_mae; normals of the unshifted DSM);
     'xy' - its real path with dsmr (sat_utils.py:239-252): mae, mae_in, mae_out and shift from register.altitude_mae_xy, mae_nr*
     from the normals of the REGISTERED DSM, and also "dx", "dy", "rdsm".
+    sun_dir (3,) = (east, north, up) towards the sun (needs a 'utm' frame): the PSNR split into sunlit and shadowed pixels by the
+    GEOMETRIC shadow of a surface model (visibility.view_visibility of the view's own depth; shadow_eps its eps).  The raster
+    marched is the first available of shadow_dsm (on `grid`), gt_dsm, fill_holes(dsm)["filled"]; "shadow_source" names it
+    ('shadow_dsm', 'gt_dsm' or 'dsm').  Every rank marches all pixels of the gathered depth: no collective.  Adds "visibility"
+    (H W,) uint8 (0 shadowed, 1 sunlit, 2 no data), "shadow_fraction" = shadowed / (shadowed + sunlit) over the pixels the mask
+    keeps (NaN without one), "psnr_sunlit" and "psnr_shadow" = image_psnr under mask AND visibility == 1 / == 0, with upstream's
+    whole-target normaliser; a class without a pixel gives -1.  sun_dir=None: nothing changes, no key and no bit.
     -> {"psnr", "psnr_scl", "ssim", "ssim_scl", "ssim_skipped", "ssim_sums", "rgb", "depth"} (+ "dsm", "count", "grid",
     "skipped" with a frame; + "mae", "mae_in", "mae_out", "mae_nr", "mae_nr_in", "mae_nr_out", "shift" with gt_dsm)."""
     from .distributed import allreduce_, row_band
@@ -212,6 +220,18 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
         raise ValueError(f"score_view: register {register!r} ('z' or 'xy')")
     if gt_dsm is not None and frame is None:
         raise ValueError("score_view: gt_dsm needs the scene's frame (frame=) to build the DSM it is compared with")
+    if sun_dir is not None:
+        if frame is None:
+            raise ValueError("score_view: sun_dir needs the scene's frame (frame=) to place the view's pixels on the surface model")
+        if frame.cs == "ecef":
+            raise ValueError("score_view: sun_dir is not served on an 'ecef' frame: its world axes are not (east, north, up)")
+        sun_dir = Fn._vis_dirs("score_view", sun_dir)
+        if sun_dir.shape[0] != 1:
+            raise ValueError(f"score_view: sun_dir is ONE direction (3,), not {tuple(sun_dir.shape)}")
+        Fn._vis_scalars("score_view", resolution, shadow_eps, 0.0)
+        if shadow_dsm is not None and grid is not None and tuple(torch.as_tensor(shadow_dsm).shape) != (grid.height, grid.width):
+            raise ValueError(f"score_view: shadow_dsm {tuple(torch.as_tensor(shadow_dsm).shape)} is not on the grid of "
+                             f"{grid.height} x {grid.width} cells")
     check_window(window, H, W)
     view = render_image(models, args, rays, None, keys=("rgb", "depth"), group=group, **render_kw)
     rgb, depth = view["rgb"], view["depth"]
@@ -241,7 +261,34 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
                 nr = normal_angle_mae(dsm, gt_dsm, grid.resolution, mask=dsm_mask)
             res.update(mae=alt["mae"], shift=alt["shift"], mae_in=alt.get("mae_in", -1), mae_out=alt.get("mae_out", -1),
                        mae_nr=nr["mae_nr"], mae_nr_in=nr["mae_nr_in"], mae_nr_out=nr["mae_nr_out"])
+        if sun_dir is not None:
+            res.update(_shadow_split(rays, rgb, rgbs, depth, mask, frame, grid, dsm, gt_dsm, shadow_dsm, sun_dir, shadow_eps, group))
     return res
+
+
+def _shadow_split(rays, rgb, rgbs, depth, mask, frame, grid, dsm, gt_dsm, shadow_dsm, sun_dir, eps, group):
+    """score_view's sun_dir keys: the geometric shadow of the view's pixels and the PSNR of either class."""
+    from .fill import fill_holes
+    from .visibility import BLOCKED, VISIBLE, view_visibility
+    if shadow_dsm is not None:
+        raster, source = torch.as_tensor(shadow_dsm).to(dsm.device), "shadow_dsm"
+        if tuple(raster.shape) != (grid.height, grid.width):
+            raise ValueError(f"score_view: shadow_dsm {tuple(raster.shape)} is not on the grid of {grid.height} x {grid.width} cells")
+    elif gt_dsm is not None:
+        raster, source = gt_dsm, "gt_dsm"
+    else:
+        raster, source = fill_holes(dsm, group=group)["filled"], "dsm"
+    vis = view_visibility(rays, depth, frame, Fn._f32(raster).contiguous(), grid, sun_dir, eps)["visible"][0]
+    keep = torch.ones_like(vis, dtype=torch.bool) if mask is None else (torch.as_tensor(mask).to(vis.device).reshape(-1) != 0)
+    if keep.numel() != vis.numel():
+        raise ValueError(f"score_view: mask of {keep.numel()} elements for {vis.numel()} pixels")
+    out = {"visibility": vis, "shadow_source": source}
+    lit, dark = keep & (vis == VISIBLE), keep & (vis == BLOCKED)
+    n_lit, n_dark = int(lit.sum()), int(dark.sum())
+    out["shadow_fraction"] = n_dark / (n_lit + n_dark) if n_lit + n_dark else float("nan")
+    out["psnr_sunlit"] = float(image_psnr(rgb, rgbs, mask=lit)[0]) if n_lit else -1
+    out["psnr_shadow"] = float(image_psnr(rgb, rgbs, mask=dark)[0]) if n_dark else -1
+    return out
 
 
 __all__ = ["image_psnr", "image_ssim", "dsm_normals", "normal_angle_mae", "score_view", "gaussian_window", "layout_strides"]

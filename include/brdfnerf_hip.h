@@ -942,6 +942,54 @@ int bn_ortho_splat(const float *rays, int64_t ray_stride, const float *depth, in
                    int32_t zone, int32_t south, const float *features, int64_t feature_stride, int32_t E, const long long *top,
                    long long band_q, long long *acc, unsigned long long *counters, void *stream);
 int bn_ortho_resolve(const long long *acc, int32_t W, int32_t H, int32_t E, float *maps, float *dsm, int32_t *count, void *stream);
+/* Visibility over a surface model (additive to ABI 7): from a start on or above a height grid, march along a direction and report
+ * whether some cell rises above the ray.  With a sun direction that is the shadow mask of the grid (or of a view's surface
+ * points), with the direction towards the sensor the view's occlusion mask.  There is NO upstream counterpart - the reference
+ * never computes a geometric shadow - so the rule is this project's own and there is nothing to check it against but its statement.
+ *
+ * Grid.  dsm is float32 [H][W], north-up (the Grid of the DSM entries): cell (j, i) covers east [xoff + i res, xoff + (i + 1) res),
+ *   row 0 is the northern edge.
+ * Direction.  d = (dx, dy, dz), float64 (east, north, up), pointing FROM the surface TOWARDS the sun or the sensor; it need not be
+ *   normalised.  dirs is [K][3] in HOST memory: the entries read and check every direction before the first launch.
+ * Everything below is float64 and every operation is rounded on its own (no fused multiply-add).
+ * Start.  Grid mode: cell (j, i) starts at u0 = i + 0.5, v0 = j + 0.5, z0 = (double)dsm[j][i].  Point mode: a point (e, n, a)
+ *   starts at u0 = (e - xoff) / res, v0 = (yoff - n) / res, z0 = a (bn_dsm_splat's two quotients without the floor).  A start
+ *   that is NaN in z0 or not finite in any coordinate is BN_VIS_NODATA; so is a point-mode start with
+ *   !(u0 >= 0 && u0 < W && v0 >= 0 && v0 < H).
+ * Slope.  a = fmax(fabs(dx), fabs(dy)).  a == 0 (the zenith): every start with data is BN_VIS_VISIBLE.  Otherwise su = dx / a,
+ *   sv = -(dy / a), sz = (dz / a) * res: one of su, sv is exactly +-1, so a step crosses exactly one cell along the dominant axis.
+ *   The start cell itself is never tested.
+ * March.  For t = 1, 2, ...:
+ *     ut = u0 + (double)t * su ;  vt = v0 + (double)t * sv ;  zt = z0 + (double)t * sz      (the product with t, never a running sum)
+ *     if !(ut >= 0 && ut < W && vt >= 0 && vt < H): the start is BN_VIS_VISIBLE, stop
+ *     h = (double)dsm[(int)floor(vt)][(int)floor(ut)]
+ *     if h > zt + eps: the start is BN_VIS_BLOCKED and hit = that cell's flat index floor(vt) W + floor(ut), stop
+ *   The comparison is strict (h == zt + eps does not block) and false for a NaN cell, which therefore never blocks; +inf blocks,
+ *   -inf never does.  The march ends after at most max(W, H) steps (by then the dominant axis has left the grid): visible.
+ * zmax is an optimisation argument: a kernel may declare a start visible as soon as zt > zmax.  With eps >= 0 and zmax >= every
+ *   non-NaN cell this cannot change a bit (h <= zmax < zt <= zt + eps); zmax = +inf is the plain rule.  A smaller zmax is the
+ *   caller's error and is not detected.
+ * Outputs.  vis uint8 [K][N] in {BN_VIS_BLOCKED, BN_VIS_VISIBLE, BN_VIS_NODATA}; hit int32 [K][N] (nullable): the flat index of the
+ *   first blocking cell in ascending t, or -1; counts int64 [K][3] = (blocked, visible, nodata) over the starts of the call, which
+ *   the CALLER zeroes and calls accumulate into, one integer atomic per counter and block.  There is no float atomic.  Every bit
+ *   depends on the grid, the starts and the directions alone - not on blocks, on row bands, on how K is split over calls, or on
+ *   the number of ranks (the counts of bands or ranks add up).
+ * bn_grid_visibility: N = H W, the starts are the cells of rows [row0, row1); vis and hit are [K][H][W] and only the band's rows
+ *   are written.  An empty band is accepted and launches nothing.
+ * bn_points_visibility: N = R, enz float64 [R][3] = (east, north, altitude) on the device.  R == 0 launches nothing.
+ * Refused (BN_EINVAL, nothing launched, buffers untouched): NULL dsm, dirs, vis, counts or enz; H or W < 1, or H W > 2^30; K outside
+ * [1, BN_VIS_MAX_DIRS]; R < 0 or over 2^30; rows outside [0, H] or row0 > row1; res not positive and finite; a non-finite grid
+ * origin; eps negative or not finite; a NaN zmax; a direction with a non-finite component or dz <= 0 (a sun below the horizon is
+ * the caller's case, not a march). */
+#define BN_VIS_BLOCKED 0
+#define BN_VIS_VISIBLE 1
+#define BN_VIS_NODATA 2
+#define BN_VIS_MAX_DIRS 4096
+int bn_grid_visibility(const float *dsm, int32_t H, int32_t W, double res, int32_t row0, int32_t row1, const double *dirs, int32_t K,
+                       double eps, double zmax, uint8_t *vis, int32_t *hit, long long *counts, void *stream);
+int bn_points_visibility(const double *enz, int64_t R, const float *dsm, int32_t H, int32_t W, double xoff, double yoff, double res,
+                         const double *dirs, int32_t K, double eps, double zmax, uint8_t *vis, int32_t *hit, long long *counts,
+                         void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
