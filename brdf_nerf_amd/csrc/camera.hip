@@ -34,13 +34,14 @@
 #include <cmath>
 #include "common.h"
 #include "brdfnerf_hip.h"
+#include "block_sums.h"
 #include "geodesy.h"
 // every float64 operation below is rounded on its own (see above); the build also passes -ffp-contract=off for this file
 #pragma clang fp contract(off)
 
 namespace {
 
-// UtmK, World, geo_world, count_block and make_world: geodesy.h, shared with world.hip
+// UtmK, World, geo_world and make_world: geodesy.h, shared with world.hip
 using namespace geodesy;
 
 constexpr int CAM_BLOCK = 256;
@@ -155,7 +156,7 @@ void rpc_localize_kernel(const bn_rpc R, const double *__restrict__ cols, const 
     lonlat[2 * k] = lon;
     lonlat[2 * k + 1] = lat;
   }
-  count_block(bad, counts);
+  block_sums::block_count(bad, counts);
 }
 
 __global__ __launch_bounds__(CAM_BLOCK)
@@ -247,7 +248,7 @@ void rpc_rays_kernel(const bn_rpc R, const World Wd, const RayArgs A) {
       out[10] = A.sun[2];
     }
   }
-  count_block(bad, A.counts);
+  block_sums::block_count(bad, A.counts);
 }
 
 // The tie-point depth priors of a view ("The depth priors of a view" in the header).  Two launches, one lane per tie point:
@@ -263,8 +264,8 @@ void tie_owner_kernel(const int32_t *__restrict__ px, int32_t T, int32_t H, int3
     outside = col < 0 || col >= W || row < 0 || row >= H;
     if (!outside) dup = atomicMax(&owner[(int64_t)row * W + col], (int32_t)t) != -1;
   }
-  count_block(outside, counts);
-  count_block(dup, counts + 1);
+  block_sums::block_count(outside, counts);
+  block_sums::block_count(dup, counts + 1);
 }
 
 struct TieArgs {
@@ -337,8 +338,8 @@ void tie_priors_kernel(const bn_rpc R, const World Wd, const TieArgs A) {
       }
     }
   }
-  count_block(skipped, A.counts + 2);
-  count_block(unsampled, A.counts + 3);
+  block_sums::block_count(skipped, A.counts + 2);
+  block_sums::block_count(unsampled, A.counts + 3);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side

@@ -84,17 +84,6 @@ __device__ __forceinline__ bool ecef_geodetic(const EcefK &K, double x, double y
   return p == 0.0 || !(isfinite(x) && isfinite(y) && isfinite(z) && isfinite(rlat) && isfinite(alt));
 }
 
-// the block's counted rows, one integer atomic (every thread of the block calls this)
-__device__ __forceinline__ void count_block(bool bad, unsigned long long *counts) {
-  __shared__ unsigned int block_bad;
-  if (threadIdx.x == 0) block_bad = 0;
-  __syncthreads();
-  const unsigned long long ballot = __ballot(bad);
-  if ((threadIdx.x & 63) == 0 && ballot) atomicAdd(&block_bad, (unsigned int)__popcll(ballot));       // LDS, integer
-  __syncthreads();
-  if (threadIdx.x == 0 && block_bad) atomicAdd(counts, (unsigned long long)block_bad);
-}
-
 // ---------------------------------------------------------------------------------------------------------------- host side
 // World of (cs, zone, south): the WGS84 constants of both coordinate systems
 inline World make_world(int32_t cs, int32_t zone, int32_t south) {

@@ -19,6 +19,7 @@
 #include <cmath>
 #include "common.h"
 #include "brdfnerf_hip.h"
+#include "block_sums.h"
 #include "normal_chain.h"
 // every float64 operation below is rounded on its own (see above); the build also passes -ffp-contract=off for this file
 #pragma clang fp contract(off)
@@ -46,16 +47,6 @@ __device__ __forceinline__ int reflect(int i, int n) {
   if (i < 0) i = -i;
   if (i >= n) i = 2 * (n - 1) - i;
   return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
-// sum of one int64 per lane over the 256 lanes of the block; valid in lane 0 of wave 0
-__device__ __forceinline__ long long block_sum(long long v, long long *red) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();                             // red may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
 }
 
 __global__ __launch_bounds__(256)
@@ -108,7 +99,7 @@ void ssim_map_kernel(const SsimArgs A, float *__restrict__ map, unsigned long lo
       skip += 1;
     }
   }
-  const long long s0 = block_sum(qsum, red), s1 = block_sum(cnt, red), s2 = block_sum(skip, red);
+  const long long s0 = block_sums::block_sum(qsum, red), s1 = block_sums::block_sum(cnt, red), s2 = block_sums::block_sum(skip, red);
   if (threadIdx.x == 0) {
     atomicAdd(sums + 0, (unsigned long long)s0);           // two's complement: a negative sum wraps
     atomicAdd(sums + 1, (unsigned long long)s1);
@@ -164,11 +155,7 @@ void normal_angle_kernel(const float *__restrict__ n1, const float *__restrict__
     }
     inside = !mask || mask[cell] != 0;
   }
-  const long long v[6] = {q, n, inside ? q : 0, inside ? n : 0, inside ? 0 : q, inside ? 0 : n};
-  for (int k = 0; k < 6; ++k) {
-    const long long s = block_sum(v[k], red);
-    if (threadIdx.x == 0 && s != 0) atomicAdd(sums + k, (unsigned long long)s);
-  }
+  block_sums::masked_sums6(q, n, inside, red, sums);
 }
 
 }  // namespace

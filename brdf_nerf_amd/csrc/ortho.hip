@@ -26,6 +26,7 @@
 #include <cmath>
 #include "common.h"
 #include "brdfnerf_hip.h"
+#include "block_sums.h"
 #include "geodesy.h"
 #include "surface_cell.h"
 // every float64 operation below is rounded on its own (see above); the build also passes -ffp-contract=off for this file
@@ -73,7 +74,7 @@ void ortho_top_kernel(const PointArgs A, const ToEnz T, const GridArgs G, long l
     if (what == POINT_DEPOSIT)
       for_footprint(G, i, j, [&](int64_t c) { __hip_atomic_fetch_max(top + c, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
   }
-  count_block(bad, skipped);
+  block_sums::block_count(bad, skipped);
 }
 
 __global__ __launch_bounds__(ORTHO_BLOCK)

@@ -26,6 +26,7 @@
 #include <cmath>
 #include "common.h"
 #include "brdfnerf_hip.h"
+#include "block_sums.h"
 // every float64 operation below is rounded on its own (see above); the build also passes -ffp-contract=off for this file
 #pragma clang fp contract(off)
 
@@ -39,16 +40,6 @@ constexpr int MAXSHIFTS = (2 * MAXR + 1) * (2 * MAXR + 1);
 constexpr double QMAX = 1048576.0;                      // 2^20: the largest quantum
 constexpr double MAE_FIX = 1048576.0;                   // 2^20
 constexpr double MAE_LIMIT = 2097152.0;                 // 2^21 m: |diff| 2^20 < 2^41, 2^22 cells of it stay below 2^63
-
-// sum of one int64 per lane over the 256 lanes of the block (as metrics.hip)
-__device__ __forceinline__ long long block_sum(long long v, long long *red) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();                             // red may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 
 __global__ __launch_bounds__(256)
 void grid_halve_kernel(const double *__restrict__ src, int H, int W, int Ho, int Wo, double *__restrict__ dst) {
@@ -146,7 +137,7 @@ void ncc_moments_kernel(const double *__restrict__ u, const double *__restrict__
     for (int g = 0; g < G; ++g) t += red[g * nsh * 6 + idx];
     if (t != 0) atomicAdd(sums + idx, (unsigned long long)t);
   }
-  const long long sk = block_sum(skip, wred);
+  const long long sk = block_sums::block_sum(skip, wred);
   if (tid == 0 && sk != 0) atomicAdd(skipped, (unsigned long long)sk);
 }
 
@@ -173,11 +164,7 @@ void dsm_shift_diff_kernel(const float *__restrict__ pred, const float *__restri
     }
     inside = !mask || mask[cell] != 0;
   }
-  const long long vals[6] = {q, n, inside ? q : 0, inside ? n : 0, inside ? 0 : q, inside ? 0 : n};
-  for (int k = 0; k < 6; ++k) {
-    const long long s = block_sum(vals[k], red);
-    if (threadIdx.x == 0 && s != 0) atomicAdd(sums + k, (unsigned long long)s);
-  }
+  block_sums::masked_sums6(q, n, inside, red, sums);
 }
 
 }  // namespace

@@ -31,6 +31,7 @@
 #include <cmath>
 #include "common.h"
 #include "brdfnerf_hip.h"
+#include "block_sums.h"
 #include "normal_chain.h"
 // every float64 operation below is rounded on its own; the build also passes -ffp-contract=off for this file
 #pragma clang fp contract(off)
@@ -52,10 +53,7 @@ struct RayArgs {
   unsigned long long *counters;
 };
 
-__device__ __forceinline__ long long wave_sum(long long v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;                                    // valid in lane 0
-}
+using block_sums::wave_sum;
 
 __global__ __launch_bounds__(RAYS)
 void ray_maps_kernel(const RayArgs A) {

@@ -40,6 +40,7 @@
 #include <cmath>
 #include "common.h"
 #include "brdfnerf_hip.h"
+#include "block_sums.h"
 #include "geodesy.h"
 #include "surface_cell.h"
 // every float64 operation below is rounded on its own (see above); the build also passes -ffp-contract=off for this file
@@ -61,7 +62,7 @@ void ecef_geodetic_kernel(const EcefK K, const double *__restrict__ xyz, int64_t
     lonlat[2 * i + 1] = bad ? __builtin_nan("") : lat;
     alt[i] = bad ? __builtin_nan("") : a;
   }
-  count_block(bad, skipped);
+  block_sums::block_count(bad, skipped);
 }
 
 __global__ __launch_bounds__(WORLD_BLOCK)
@@ -75,7 +76,7 @@ void surface_points_kernel(const PointArgs A, const ToEnz T, double *__restrict_
     enz[3 * ray + 1] = n;
     enz[3 * ray + 2] = a;
   }
-  count_block(bad, skipped);
+  block_sums::block_count(bad, skipped);
 }
 
 __global__ __launch_bounds__(WORLD_BLOCK)
@@ -87,10 +88,10 @@ void dsm_splat_points_kernel(const double *__restrict__ enz, int64_t stride, int
     const double *p = enz + i * stride;
     bad = deposit(G, p[0], p[1], p[2], acc);
   }
-  count_block(bad, skipped);
+  block_sums::block_count(bad, skipped);
 }
 
-// ECEF: the conversion is compiled in (and taken when T.ecef says so) or out.  No lane returns before count_block
+// ECEF: the conversion is compiled in (and taken when T.ecef says so) or out.  No lane returns before block_count
 template <bool ECEF> __global__ __launch_bounds__(WORLD_BLOCK)
 void dsm_splat_world_kernel(const PointArgs A, const ToEnz T, const GridArgs G, unsigned long long *__restrict__ acc,
                             unsigned long long *__restrict__ skipped) {
@@ -101,7 +102,7 @@ void dsm_splat_world_kernel(const PointArgs A, const ToEnz T, const GridArgs G, 
     surface_point<ECEF>(A, T, ray, e, n, a);       // a refused point is NaN, which deposit skips
     bad = deposit(G, e, n, a, acc);
   }
-  count_block(bad, skipped);
+  block_sums::block_count(bad, skipped);
 }
 
 __global__ __launch_bounds__(WORLD_BLOCK)

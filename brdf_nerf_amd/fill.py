@@ -40,7 +40,7 @@ def fill_holes(dsm, rows=None, group=None, want_source=False):
     -> {"filled" (H, W) float32, "holes" int, "max_dist" float = sqrt(largest d2)} (+ "source" (H, W) int32 flat indices)."""
     import torch.distributed as dist
     from .distributed import allreduce_, gather_rows, row_band, world_info
-    Fn._fill_grid("fill_holes", dsm, torch.float32, "dsm")
+    Fn._need("fill_holes", dsm, "dsm", torch.float32, **Fn.FILL_GRID)
     H, W = dsm.shape
     _, world = world_info(group)
     rows = row_band("fill_holes", H, rows, group)

@@ -728,12 +728,86 @@ def ray_shade_dirs(desc, acc, wsum, rays_d, sun, view=None, rgb=None, brdf=None,
     return rgb, brdf
 
 
+# ------------------------------------------------------------------------------ the evaluation entries
+def _need(name, t, what, dtype, shape=None, contiguous=True, side=None, cells=None):
+    """The one tensor check of the entries that run after training (down to point_normals, and the relighting ones): the C entry
+    points see raw pointers, so `t` is a tensor of `dtype` and `shape` or ValueError "<name>: <what> ...", under python -O too.
+    shape: a tuple whose int entries must match, ">= n" entries are lower bounds and other strings name free entries; an int: that
+    many elements in any shape; None: any.  contiguous: True (required), "copy" / "rows" (a tensor that is not contiguous / whose
+    rows do not have unit inner stride is copied, as the wrappers always did) or False (any strides).  side / cells = (lo, hi):
+    bounds on every free entry / on their product.  -> t or its copy.  The device is _on_device's, last."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: {what} must be a tensor on the device (there is no host path)")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: {what} is {t.dtype}, not {dtype}")
+    if isinstance(shape, tuple):
+        fits = lambda w, h: h == w if isinstance(w, int) else (not w.startswith(">=") or h >= int(w[2:]))
+        ok = t.dim() == len(shape) and all(fits(w, h) for w, h in zip(shape, t.shape))
+        form = f"{len(shape)}-D tensor of shape ({', '.join(str(w) for w in shape)})"
+    else:
+        ok, form = shape is None or t.numel() == shape, "tensor" if shape is None else f"tensor of {shape} elements"
+    if not ok or (contiguous is True and not t.is_contiguous()):
+        raise ValueError(f"{name}: {what} {tuple(t.shape)} is not a {'contiguous ' if contiguous is True else ''}{form}")
+    free = [h for w, h in zip(shape, t.shape) if not isinstance(w, int)] if isinstance(shape, tuple) else []
+    for bounds, sizes, unit in ((side, free, "cells a side"), (cells, [math.prod(free)], "cells")):
+        if bounds is not None and not all(bounds[0] <= s <= bounds[1] for s in sizes):
+            raise ValueError(f"{name}: {what} {tuple(t.shape)} ({bounds[0]} to {bounds[1]} {unit})")
+    if contiguous == "copy" or (contiguous == "rows" and t.shape[-1] > 1 and t.stride(-1) != 1):
+        return t.contiguous()
+    return t
+
+
+def _maybe(name, t, *spec, **kw):
+    """_need for an optional input: None stays None."""
+    return None if t is None else _need(name, t, *spec, **kw)
+
+
+def _out(name, t, what, dtype, shape, device, make=torch.zeros, flat=False):
+    """An optional output or accumulator: made (zeroed, unless `make` says otherwise) when None, otherwise checked - by its shape,
+    or with `flat` by its number of elements."""
+    return make(shape, dtype=dtype, device=device) if t is None else _need(name, t, what, dtype, math.prod(shape) if flat else shape)
+
+
+def _on_device(name, *tensors):
+    """The last of the host-side checks, so that a host tensor is refused by what else is wrong with the call first."""
+    if not all(t.is_cuda for t in tensors if t is not None):
+        raise ValueError(f"{name}: every tensor must be on the device (there is no host path)")
+
+
+F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
+FILL_GRID = dict(shape=("H", "W"), side=(1, L.BN_FILL_MAX_SIDE))                          # a grid of the hole filling
+VIS_DSM = dict(what="dsm", dtype=F32, shape=("H", "W"), cells=(1, 1 << 30))               # the height grid of the visibility entries
+VIS_POINTS = dict(what="points", dtype=F64, shape=("R", 3), contiguous="copy", cells=(0, 1 << 30))      # point_cloud's output
+
+
+def fixed_mean(total, count, fix):
+    """The mean that an integer (sum of llrint(v fix), count) pair stands for; Python integers in, NaN for a zero count."""
+    return total / (count * fix) if count else float("nan")
+
+
+def _ray_rows(name, rays, depth):
+    """rays (R, >= 6) float32 rows with unit inner stride and depth (R,) float32, copied where they are not -> rays, depth, R and
+    the row stride."""
+    rays = _need(name, rays, "rays", F32, ("R", ">=6"), "rows")
+    R = rays.shape[0]
+    depth = _need(name, depth, "depth", F32, (R,), "copy")
+    return rays, depth, R, (rays.stride(0) if R > 1 else rays.shape[1])       # (one row: its stride is not read)
+
+
+def _dsm_acc(name, acc, skipped, *others):
+    """The (H, W, 2) int64 accumulator and the (1,) int64 counter of the DSM splats, then the device of all -> H, W."""
+    _need(name, acc, "acc", I64, ("H", "W", 2))
+    _need(name, skipped, "skipped", I64, 1)
+    _on_device(name, acc, skipped, *others)
+    return acc.shape[0], acc.shape[1]
+
+
 def dsm_splat(rays, depth, center, rng, xoff, yoff, resolution, radius, footprint, acc, skipped):
     """The depths of R rays splatted into a DSM accumulator (bn_dsm_splat).  rays (R, >= 6) float32 rows with unit inner stride
     (origin, direction), depth (R,) float32; center (3 floats) and rng the scene normalisation, (xoff, yoff) the grid's north-west
     corner; acc (H, W, 2) int64 = (sum, count) and skipped (1,) int64 on the device, accumulated into."""
-    rays, depth, R, stride = _ray_rows(rays, depth)
-    H, W = _dsm_acc(acc, skipped)
+    rays, depth, R, stride = _ray_rows("dsm_splat", rays, depth)
+    H, W = _dsm_acc("dsm_splat", acc, skipped, rays, depth)
     if R == 0:
         return acc
     with torch.cuda.device(rays.device):
@@ -741,24 +815,6 @@ def dsm_splat(rays, depth, center, rng, xoff, yoff, resolution, radius, footprin
                                      *_abi_args((center, rng), (xoff, yoff, resolution, W, H, radius, footprint)), _p(acc), _p(skipped),
                                      _stream()), "bn_dsm_splat")
     return acc
-
-
-def _ray_rows(rays, depth):
-    R = rays.shape[0]
-    assert rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] >= 6
-    assert depth.is_cuda and depth.dtype == torch.float32 and depth.shape == (R,)
-    rays = rays if rays.stride(1) == 1 else rays.contiguous()
-    return rays, depth.contiguous(), R, (rays.stride(0) if R > 1 else rays.shape[1])       # (one row: its stride is not read)
-
-
-def _counter(t, n=1):
-    assert t.is_cuda and t.dtype == torch.int64 and t.numel() == n and t.is_contiguous()
-
-
-def _dsm_acc(acc, skipped):
-    assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] == 2 and acc.is_contiguous()
-    _counter(skipped)
-    return acc.shape[0], acc.shape[1]
 
 
 def _abi_args(frame=(), grid=(), world=()):
@@ -771,9 +827,9 @@ def _abi_args(frame=(), grid=(), world=()):
 def ecef_geodetic(xyz, skipped):
     """Geodetic points of ECEF points (bn_ecef_geodetic): xyz (n, 3) float64 -> lonlat (n, 2) in degrees, alt (n,) float64, NaN
     where a point is refused (on the axis or not finite); skipped (1,) int64 on the device, accumulated into."""
-    assert xyz.is_cuda and xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.shape[1] == 3
-    _counter(skipped)
-    xyz = xyz.contiguous()
+    xyz = _need("ecef_geodetic", xyz, "xyz", F64, ("n", 3), "copy")
+    _need("ecef_geodetic", skipped, "skipped", I64, 1)
+    _on_device("ecef_geodetic", xyz, skipped)
     n = xyz.shape[0]
     lonlat = torch.empty((n, 2), dtype=torch.float64, device=xyz.device)
     alt = torch.empty((n,), dtype=torch.float64, device=xyz.device)
@@ -788,8 +844,9 @@ def surface_points(rays, depth, center, rng, cs, zone, south, skipped):
     """(east, north, altitude) of R rays' surface points (bn_surface_points): rays (R, >= 6) float32 rows with unit inner stride,
     depth (R,) float32; cs BN_CS_ECEF or BN_CS_UTM, the scene's zone -> float64 (R, 3), NaN where a row is refused; skipped (1,)
     int64 on the device, accumulated into."""
-    rays, depth, R, stride = _ray_rows(rays, depth)
-    _counter(skipped)
+    rays, depth, R, stride = _ray_rows("surface_points", rays, depth)
+    _need("surface_points", skipped, "skipped", I64, 1)
+    _on_device("surface_points", rays, depth, skipped)
     enz = torch.empty((R, 3), dtype=torch.float64, device=rays.device)
     if R == 0:
         return enz
@@ -803,12 +860,10 @@ def surface_points(rays, depth, center, rng, cs, zone, south, skipped):
 def dsm_splat_points(enz, xoff, yoff, resolution, radius, footprint, acc, skipped):
     """World points that already are (east, north, altitude) splatted into a DSM accumulator (bn_dsm_splat_points): enz (n, >= 3)
     float64 rows with unit inner stride; acc and skipped as dsm_splat."""
-    assert enz.is_cuda and enz.dtype == torch.float64 and enz.dim() == 2 and enz.shape[1] >= 3
-    H, W = _dsm_acc(acc, skipped)
+    enz = _need("dsm_splat_points", enz, "enz", F64, ("n", ">=3"), "rows")
+    H, W = _dsm_acc("dsm_splat_points", acc, skipped, enz)
     if enz.shape[0] == 0:
         return acc
-    if enz.stride(1) != 1:
-        enz = enz.contiguous()
     with torch.cuda.device(enz.device):
         L.check(L.lib().bn_dsm_splat_points(C.c_void_p(enz.data_ptr()), enz.stride(0) if enz.shape[0] > 1 else enz.shape[1], enz.shape[0],
                                             *_abi_args(grid=(xoff, yoff, resolution, W, H, radius, footprint)), _p(acc), _p(skipped),
@@ -819,8 +874,8 @@ def dsm_splat_points(enz, xoff, yoff, resolution, radius, footprint, acc, skippe
 def dsm_splat_world(rays, depth, center, rng, xoff, yoff, resolution, radius, footprint, cs, zone, south, acc, skipped):
     """dsm_splat for a scene whose world points are `cs` (bn_dsm_splat_world): ray -> world point -> (east, north, altitude) ->
     deposit in one launch."""
-    rays, depth, R, stride = _ray_rows(rays, depth)
-    H, W = _dsm_acc(acc, skipped)
+    rays, depth, R, stride = _ray_rows("dsm_splat_world", rays, depth)
+    H, W = _dsm_acc("dsm_splat_world", acc, skipped, rays, depth)
     if R == 0:
         return acc
     with torch.cuda.device(rays.device):
@@ -834,9 +889,10 @@ def ortho_top(rays, depth, center, rng, xoff, yoff, resolution, radius, footprin
     """Pass 1 of the orthorectified maps (bn_ortho_top): top (H, W) int64, filled with BN_ORTHO_EMPTY by the caller, takes the
     maximum of the quantised altitudes over every ray's footprint; rays, depth, the frame and the grid as dsm_splat_world; skipped
     (1,) int64 on the device, accumulated into."""
-    rays, depth, R, stride = _ray_rows(rays, depth)
-    assert top.is_cuda and top.dtype == torch.int64 and top.dim() == 2 and top.is_contiguous()
-    _counter(skipped)
+    rays, depth, R, stride = _ray_rows("ortho_top", rays, depth)
+    _need("ortho_top", top, "top", I64, ("H", "W"))
+    _need("ortho_top", skipped, "skipped", I64, 1)
+    _on_device("ortho_top", rays, depth, top, skipped)
     if R == 0:
         return top
     H, W = top.shape
@@ -853,19 +909,21 @@ def ortho_splat(rays, depth, center, rng, xoff, yoff, resolution, radius, footpr
     a wider tensor is read in place; None with E == 0) deposited with the altitude into acc (H, W, 2 + E) int64 = (sum_z, count,
     sum_0 ...), accumulated into; top (H, W) int64 of ortho_top or None (mean mode), band_q in units of 2^-20 m; counters (3,)
     int64 on the device = (bad points, bad features, culled deposits), accumulated into."""
-    rays, depth, R, stride = _ray_rows(rays, depth)
-    assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] >= 2 and acc.is_contiguous()
+    name = "ortho_splat"
+    rays, depth, R, stride = _ray_rows(name, rays, depth)
+    _need(name, acc, "acc", I64, ("H", "W", ">=2"))
     H, W, E = acc.shape[0], acc.shape[1], acc.shape[2] - 2
-    _counter(counters, 3)
-    assert top is None or (top.is_cuda and top.dtype == torch.int64 and top.shape == (H, W) and top.is_contiguous())
+    _need(name, counters, "counters", I64, 3)
+    _maybe(name, top, "top", I64, (H, W))
     if E == 0:
-        assert features is None or (features.dim() == 2 and features.shape == (R, 0))
-        fp, fs = None, 0
+        if features is not None and tuple(features.shape) != (R, 0):
+            raise ValueError(f"{name}: features {tuple(features.shape)} for an accumulator without channels")
+        features = None
     else:
-        assert features is not None and features.is_cuda and features.dtype == torch.float32 and features.shape == (R, E)
-        if features.stride(1) != 1 and E > 1:
-            features = features.contiguous()
-        fp, fs = C.c_void_p(features.data_ptr()), (features.stride(0) if R > 1 else E)       # (one row: its stride is not read)
+        features = _need(name, features, "features", F32, (R, E), "rows")
+    _on_device(name, rays, depth, acc, counters, top, features)
+    fp = None if E == 0 else C.c_void_p(features.data_ptr())
+    fs = 0 if E == 0 else (features.stride(0) if R > 1 else E)       # (one row: its stride is not read)
     if R == 0:
         return acc
     with torch.cuda.device(rays.device):
@@ -878,7 +936,8 @@ def ortho_splat(rays, depth, center, rng, xoff, yoff, resolution, radius, footpr
 def ortho_resolve(acc, want_count=True):
     """The means of an accumulator of orthorectified maps (bn_ortho_resolve): acc (H, W, 2 + E) int64 -> maps (E, H, W) float32,
     dsm (H, W) float32, both NaN where no point fell, and count (H, W) int32 (or None)."""
-    assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] >= 2 and acc.is_contiguous()
+    _need("ortho_resolve", acc, "acc", I64, ("H", "W", ">=2"))
+    _on_device("ortho_resolve", acc)
     H, W, E = acc.shape[0], acc.shape[1], acc.shape[2] - 2
     maps = torch.empty((E, H, W), dtype=torch.float32, device=acc.device)
     dsm = torch.empty((H, W), dtype=torch.float32, device=acc.device)
@@ -891,7 +950,8 @@ def ortho_resolve(acc, want_count=True):
 def dsm_resolve(acc, want_count=True):
     """Mean altitude per cell of a DSM accumulator (bn_dsm_resolve): acc (H, W, 2) int64 -> dsm (H, W) float32, NaN where no
     point fell, and count (H, W) int32 (or None)."""
-    assert acc.is_cuda and acc.dtype == torch.int64 and acc.dim() == 3 and acc.shape[2] == 2 and acc.is_contiguous()
+    _need("dsm_resolve", acc, "acc", I64, ("H", "W", 2))
+    _on_device("dsm_resolve", acc)
     H, W = acc.shape[0], acc.shape[1]
     dsm = torch.empty((H, W), dtype=torch.float32, device=acc.device)
     count = torch.empty((H, W), dtype=torch.int32, device=acc.device) if want_count else None
@@ -907,12 +967,16 @@ def ssim_map(pred, gt, C_, H, W, strides, mask, div, max_val, window, g, sums, r
     (default all); out (C, H, W) float32 map or None."""
     sp, sr, sc = (int(s) for s in strides)
     last = (C_ - 1) * sp + (H - 1) * sr + (W - 1) * sc
-    for t in (pred, gt):
-        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and min(sp, sr, sc) >= 0 and last < t.numel()
-    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == (H, W) and mask.is_contiguous())
-    assert sums.is_cuda and sums.dtype == torch.int64 and sums.numel() == 3 and sums.is_contiguous()
-    assert out is None or (out.is_cuda and out.dtype == torch.float32 and out.shape == (C_, H, W) and out.is_contiguous())
-    assert len(g) == window
+    for t, what in ((pred, "pred"), (gt, "gt")):
+        _need("ssim_map", t, what, F32)
+        if min(sp, sr, sc) < 0 or last >= t.numel():
+            raise ValueError(f"ssim_map: {what} of {t.numel()} elements is read through the strides {(sp, sr, sc)} up to element {last}")
+    _maybe("ssim_map", mask, "mask", U8, (H, W))
+    _need("ssim_map", sums, "sums", I64, 3)
+    _maybe("ssim_map", out, "out", F32, (C_, H, W))
+    if len(g) != window:
+        raise ValueError(f"ssim_map: {len(g)} weights for a window of {window}")
+    _on_device("ssim_map", pred, gt, mask, sums, out)
     row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
     gw = (C.c_double * window)(*[float(v) for v in g])
     L.check(L.lib().bn_ssim_map(_p(pred), _p(gt), C_, H, W, sp, sr, sc, _p(mask), float(div), float(max_val), int(window), gw, row0, row1,
@@ -923,8 +987,8 @@ def ssim_map(pred, gt, C_, H, W, strides, mask, div, max_val, window, g, sums, r
 def grid_normals(z, resolution):
     """The reference's four-cross-product normals of an altitude grid (bn_grid_normals): z (H, W) float32 -> (H, W, 3) float32,
     zero on the border.  y grows with the row, as upstream: flat ground gives (0, 0, -1)."""
-    assert z.is_cuda and z.dtype == torch.float32 and z.dim() == 2
-    z = z.contiguous()
+    z = _need("grid_normals", z, "z", F32, ("H", "W"), "copy")
+    _on_device("grid_normals", z)
     H, W = z.shape
     out = torch.empty((H, W, 3), dtype=torch.float32, device=z.device)
     L.check(L.lib().bn_grid_normals(_p(z), H, W, float(resolution), _p(out), _stream()), "bn_grid_normals")
@@ -935,13 +999,12 @@ def normal_angle(n1, n2, mask=None, border=0, sums=None, want_map=True):
     """The angle in degrees between two normal grids (bn_normal_angle): n1, n2 (H, W, 3) float32, mask (H, W) uint8 (nonzero:
     inside) or None -> angle (H, W) float32 (or None), sums (6,) int64 = (sum of llrint(a 2^20), count) over all, inside and
     outside cells, NaN cells left out.  border 0: the reference's (zero border normals: 90 degrees); 1: the border is NaN."""
-    H, W = n1.shape[0], n1.shape[1]
-    for t in (n1, n2):
-        assert t.is_cuda and t.dtype == torch.float32 and t.shape == (H, W, 3) and t.is_contiguous()
-    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == (H, W) and mask.is_contiguous())
-    if sums is None:
-        sums = torch.zeros((6,), dtype=torch.int64, device=n1.device)
-    assert sums.is_cuda and sums.dtype == torch.int64 and sums.numel() == 6 and sums.is_contiguous()
+    name = "normal_angle"
+    H, W = _need(name, n1, "n1", F32, ("H", "W", 3)).shape[:2]
+    _need(name, n2, "n2", F32, (H, W, 3))
+    _maybe(name, mask, "mask", U8, (H, W))
+    sums = _out(name, sums, "sums", I64, (6,), n1.device, flat=True)
+    _on_device(name, n1, n2, mask, sums)
     angle = torch.empty((H, W), dtype=torch.float32, device=n1.device) if want_map else None
     L.check(L.lib().bn_normal_angle(_p(n1), _p(n2), H, W, _p(mask), int(border), _p(angle), _p(sums), _stream()), "bn_normal_angle")
     return angle, sums
@@ -950,8 +1013,8 @@ def normal_angle(n1, n2, mask=None, border=0, sums=None, want_map=True):
 def grid_halve(src):
     """One level of the registration pyramid (bn_grid_halve): src (H, W) float64 -> (ceil(H / 2), ceil(W / 2)) float64, the mean of
     the finite cells of upstream's 2 x 2 box, NaN where there is none."""
-    assert src.is_cuda and src.dtype == torch.float64 and src.dim() == 2
-    src = src.contiguous()
+    src = _need("grid_halve", src, "src", F64, ("H", "W"), "copy")
+    _on_device("grid_halve", src)
     H, W = src.shape
     out = torch.empty(((H + 1) // 2, (W + 1) // 2), dtype=torch.float64, device=src.device)
     L.check(L.lib().bn_grid_halve(_p(src), H, W, _p(out), _stream()), "bn_grid_halve")
@@ -962,16 +1025,13 @@ def ncc_moments(u, v, pivot, k, dx0, dy0, r, sums=None, skipped=None, rows=None)
     """The integer moments of every shift of a (2r + 1)^2 window around (dx0, dy0) (bn_ncc_moments): u, v (H, W) float64 on the
     device -> sums ((2r + 1)^2, 6) int64 = (N, Su, Sv, Suu, Svv, Suv) in scan order (dy outer, dx inner) and skipped (1,) int64,
     both accumulated into when given; rows = (row0, row1) rows of u (default all)."""
-    H, W = u.shape
-    for t in (u, v):
-        assert t.is_cuda and t.dtype == torch.float64 and t.shape == (H, W) and t.is_contiguous()
+    name = "ncc_moments"
+    H, W = _need(name, u, "u", F64, ("H", "W")).shape
+    _need(name, v, "v", F64, (H, W))
     n = (2 * int(r) + 1) ** 2 if 0 <= int(r) <= L.BN_NCC_MAX_RANGE else 1          # a refused r never reaches the kernel
-    if sums is None:
-        sums = torch.zeros((n, 6), dtype=torch.int64, device=u.device)
-    if skipped is None:
-        skipped = torch.zeros((1,), dtype=torch.int64, device=u.device)
-    assert sums.is_cuda and sums.dtype == torch.int64 and sums.numel() == n * 6 and sums.is_contiguous()
-    assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() == 1
+    sums = _out(name, sums, "sums", I64, (n, 6), u.device, flat=True)
+    skipped = _out(name, skipped, "skipped", I64, (1,), u.device, flat=True)
+    _on_device(name, u, v, sums, skipped)
     row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
     L.check(L.lib().bn_ncc_moments(_p(u), _p(v), H, W, float(pivot), int(k), int(dx0), int(dy0), int(r), row0, row1, _p(sums),
                                    _p(skipped), _stream()), "bn_ncc_moments")
@@ -982,13 +1042,12 @@ def dsm_shift_diff(pred, gt, dx, dy, b, mask=None, sums=None, want_maps=True):
     """A DSM shifted by (dx, dy) cells and b metres and its difference to the ground truth (bn_dsm_shift_diff): pred, gt (H, W)
     float32, mask (H, W) uint8 (nonzero: inside) or None -> rdsm, diff (H, W) float32 (or None, None), sums (6,) int64 = (sum of
     llrint(|diff| 2^20), count) over all, inside and outside cells, NaN cells left out."""
-    H, W = pred.shape
-    for t in (pred, gt):
-        assert t.is_cuda and t.dtype == torch.float32 and t.shape == (H, W) and t.is_contiguous()
-    assert mask is None or (mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == (H, W) and mask.is_contiguous())
-    if sums is None:
-        sums = torch.zeros((6,), dtype=torch.int64, device=pred.device)
-    assert sums.is_cuda and sums.dtype == torch.int64 and sums.numel() == 6 and sums.is_contiguous()
+    name = "dsm_shift_diff"
+    H, W = _need(name, pred, "pred", F32, ("H", "W")).shape
+    _need(name, gt, "gt", F32, (H, W))
+    _maybe(name, mask, "mask", U8, (H, W))
+    sums = _out(name, sums, "sums", I64, (6,), pred.device, flat=True)
+    _on_device(name, pred, gt, mask, sums)
     rdsm = torch.empty((H, W), dtype=torch.float32, device=pred.device) if want_maps else None
     diff = torch.empty((H, W), dtype=torch.float32, device=pred.device) if want_maps else None
     L.check(L.lib().bn_dsm_shift_diff(_p(pred), _p(gt), H, W, int(dx), int(dy), float(b), _p(mask), _p(rdsm), _p(diff), _p(sums),
@@ -996,32 +1055,11 @@ def dsm_shift_diff(pred, gt, dx, dy, b, mask=None, sums=None, want_maps=True):
     return rdsm, diff, sums
 
 
-def _fill_grid(name, t, dtype, what, shape=None):
-    """A (H, W) contiguous tensor of `dtype`, 1 to BN_FILL_MAX_SIDE cells a side, or ValueError by name."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name}: {what} must be a tensor on the device (there is no host path)")
-    if t.dtype != dtype:
-        raise ValueError(f"{name}: {what} is {t.dtype}, not {dtype}")
-    if t.dim() != 2 or not t.is_contiguous():
-        raise ValueError(f"{name}: {what} {tuple(t.shape)} is not a contiguous 2-D (H, W) grid")
-    if not (1 <= t.shape[0] <= L.BN_FILL_MAX_SIDE and 1 <= t.shape[1] <= L.BN_FILL_MAX_SIDE):
-        raise ValueError(f"{name}: {what} of {t.shape[0]} x {t.shape[1]} cells (1 to {L.BN_FILL_MAX_SIDE} a side)")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: {what} {tuple(t.shape)} is not on the grid {tuple(shape)}")
-    return t
-
-
-def _fill_device(name, *tensors):
-    """The last of the host-side checks, so that a host tensor is refused by what else is wrong with the call first."""
-    if not all(t.is_cuda for t in tensors):
-        raise ValueError(f"{name}: the grids must be on the device (there is no host path)")
-
-
 def grid_nearest_col(src):
     """The column pass of the hole filling (bn_grid_nearest_col): src (H, W) float32 -> near_row (H, W) int32, per cell the row of
     the nearest known (not NaN) cell of its column, ties to the smaller row, -1 in a column without one."""
-    _fill_grid("grid_nearest_col", src, torch.float32, "src")
-    _fill_device("grid_nearest_col", src)
+    _need("grid_nearest_col", src, "src", F32, **FILL_GRID)
+    _on_device("grid_nearest_col", src)
     H, W = src.shape
     near_row = torch.empty((H, W), dtype=torch.int32, device=src.device)
     L.check(L.lib().bn_grid_nearest_col(_p(src), H, W, _p(near_row), _stream()), "bn_grid_nearest_col")
@@ -1032,13 +1070,15 @@ def grid_fill(src, near_row, rows=None, want_source=False, want_dist2=False):
     """The row pass of the hole filling (bn_grid_fill): src (H, W) float32 and its grid_nearest_col -> dst (H, W) float32 (every cell
     the bits of its nearest known cell), source (H, W) int32 flat index of that cell and dist2 (H, W) int32 (or None), counts (2,)
     int64 = (holes, largest d2).  rows = (row0, row1): only those rows are written (the others are uninitialised) and counted."""
-    _fill_grid("grid_fill", src, torch.float32, "src")
-    _fill_grid("grid_fill", near_row, torch.int32, "near_row", src.shape)
+    _need("grid_fill", src, "src", F32, **FILL_GRID)
+    _need("grid_fill", near_row, "near_row", I32, **FILL_GRID)
+    if near_row.shape != src.shape:
+        raise ValueError(f"grid_fill: near_row {tuple(near_row.shape)} is not on the grid {tuple(src.shape)}")
     H, W = src.shape
     row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
     if not 0 <= row0 <= row1 <= H:
         raise ValueError(f"grid_fill: rows ({row0}, {row1}) outside [0, {H}]")
-    _fill_device("grid_fill", src, near_row)
+    _on_device("grid_fill", src, near_row)
     dst = torch.empty((H, W), dtype=torch.float32, device=src.device)
     source = torch.empty((H, W), dtype=torch.int32, device=src.device) if want_source else None
     dist2 = torch.empty((H, W), dtype=torch.int32, device=src.device) if want_dist2 else None
@@ -1046,30 +1086,6 @@ def grid_fill(src, near_row, rows=None, want_source=False, want_dist2=False):
     L.check(L.lib().bn_grid_fill(_p(src), _p(near_row), H, W, row0, row1, _p(dst), _p(source), _p(dist2), _p(counts), _stream()),
             "bn_grid_fill")
     return dst, source, dist2, counts
-
-
-def _vis_grid(name, dsm):
-    """The height grid of the visibility entries: (H, W) float32, contiguous, H W at most 2^30, or ValueError by name."""
-    if not isinstance(dsm, torch.Tensor):
-        raise ValueError(f"{name}: dsm must be a tensor on the device (there is no host path)")
-    if dsm.dtype != torch.float32:
-        raise ValueError(f"{name}: dsm is {dsm.dtype}, not torch.float32")
-    if dsm.dim() != 2 or not dsm.is_contiguous():
-        raise ValueError(f"{name}: dsm {tuple(dsm.shape)} is not a contiguous 2-D (H, W) grid")
-    if dsm.shape[0] < 1 or dsm.shape[1] < 1 or dsm.shape[0] * dsm.shape[1] > 1 << 30:
-        raise ValueError(f"{name}: dsm of {dsm.shape[0]} x {dsm.shape[1]} cells (H W from 1 to 2^30)")
-    return dsm
-
-
-def _vis_points(name, points):
-    """The starts of point mode: (R, 3) float64, R at most 2^30, or ValueError by name; the device is checked by _fill_device, last."""
-    if not isinstance(points, torch.Tensor):
-        raise ValueError(f"{name}: points must be a tensor on the device (there is no host path)")
-    if points.dtype != torch.float64:
-        raise ValueError(f"{name}: points are {points.dtype}, not torch.float64 (point_cloud's output)")
-    if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] > 1 << 30:
-        raise ValueError(f"{name}: points {tuple(points.shape)} are not (R, 3) with R at most 2^30")
-    return points
 
 
 def _vis_dirs(name, dirs):
@@ -1105,7 +1121,7 @@ def grid_visibility(dsm, res, dirs, eps=0.0, zmax=float("inf"), rows=None, vis=N
     others are uninitialised unless `vis` / `hit` come in) and counted.  vis (K, H, W) uint8, hit (K, H, W) int32 and counts (K, 3)
     int64 may be given - counts are accumulated into.  -> vis, hit or None (want_hit, or `hit` given), counts."""
     name = "grid_visibility"
-    _vis_grid(name, dsm)
+    _need(name, dsm, **VIS_DSM)
     dirs = _vis_dirs(name, dirs)
     res, eps, zmax = _vis_scalars(name, res, eps, zmax)
     H, W = dsm.shape
@@ -1113,17 +1129,11 @@ def grid_visibility(dsm, res, dirs, eps=0.0, zmax=float("inf"), rows=None, vis=N
     row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
     if not 0 <= row0 <= row1 <= H:
         raise ValueError(f"{name}: rows ({row0}, {row1}) outside [0, {H}]")
-    for t, dtype, shape, what in ((vis, torch.uint8, (K, H, W), "vis"), (hit, torch.int32, (K, H, W), "hit"), (counts, torch.int64, (K, 3), "counts")):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
-            raise ValueError(f"{name}: {what} must be a contiguous {dtype} tensor of shape {shape}")
-    _fill_device(name, dsm, *(t for t in (vis, hit, counts) if t is not None))
-    dev = dsm.device
-    if vis is None:
-        vis = torch.empty((K, H, W), dtype=torch.uint8, device=dev)
-    if hit is None and want_hit:
-        hit = torch.empty((K, H, W), dtype=torch.int32, device=dev)
-    if counts is None:
-        counts = torch.zeros((K, 3), dtype=torch.int64, device=dev)
+    vis = _out(name, vis, "vis", U8, (K, H, W), dsm.device, torch.empty)
+    if hit is not None or want_hit:
+        hit = _out(name, hit, "hit", I32, (K, H, W), dsm.device, torch.empty)
+    counts = _out(name, counts, "counts", I64, (K, 3), dsm.device)
+    _on_device(name, dsm, vis, hit, counts)
     L.check(L.lib().bn_grid_visibility(_p(dsm), H, W, res, row0, row1, dirs.numpy().ctypes.data_as(C.POINTER(C.c_double)), K, eps, zmax,
                                        _p(vis), _p(hit), _p(counts), _stream()), "bn_grid_visibility")
     return vis, hit, counts
@@ -1134,15 +1144,14 @@ def points_visibility(points, dsm, xoff, yoff, res, dirs, eps=0.0, zmax=float("i
     the device (point_cloud's output), dsm (H, W) float32 with its Grid's origin and resolution, dirs (K, 3).
     -> vis (K, R) uint8, hit (K, R) int32 or None, counts (K, 3) int64."""
     name = "points_visibility"
-    _vis_points(name, points)
-    _vis_grid(name, dsm)
+    points = _need(name, points, **VIS_POINTS)
+    _need(name, dsm, **VIS_DSM)
     dirs = _vis_dirs(name, dirs)
     res, eps, zmax = _vis_scalars(name, res, eps, zmax)
     xoff, yoff = float(xoff), float(yoff)
     if not (math.isfinite(xoff) and math.isfinite(yoff)):
         raise ValueError(f"{name}: grid origin ({xoff}, {yoff}) is not finite")
-    _fill_device(name, points, dsm)
-    points = points.contiguous()
+    _on_device(name, points, dsm)
     H, W = dsm.shape
     R, K = points.shape[0], dirs.shape[0]
     vis = torch.empty((K, R), dtype=torch.uint8, device=dsm.device)
@@ -1157,19 +1166,6 @@ def points_visibility(points, dsm, xoff, yoff, res, dirs, eps=0.0, zmax=float("i
 RAY_MAP_COUNTERS = ("std_sum", "std_count", "std_skipped", "bad_nr", "nr0", "nr_total")
 
 
-def _maps_f32(name, t, what, shape=None, contiguous=True):
-    """A float32 tensor of `shape` (None entries are free), or ValueError by name; the device is checked by _fill_device, last."""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name}: {what} must be a tensor on the device (there is no host path)")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name}: {what} is {t.dtype}, not torch.float32")
-    if shape is not None and (t.dim() != len(shape) or any(w is not None and int(w) != int(h) for w, h in zip(shape, t.shape))):
-        raise ValueError(f"{name}: {what} {tuple(t.shape)} does not have the shape {tuple('*' if w is None else w for w in shape)}")
-    if contiguous and not t.is_contiguous():
-        raise ValueError(f"{name}: {what} {tuple(t.shape)} is not contiguous")
-    return t
-
-
 def ray_maps(z_vals, weights, depth, X=None, accumulate=False, normal_col=None, view=None, counters=None, want_surf=True):
     """The per-ray reductions over the depth-sorted samples (bn_ray_maps).  z_vals, weights (R, S) and depth (R,) float32,
     contiguous; X (R, S, E) float32 with any non-negative strides (a column slice of the field rows is read in place) or None;
@@ -1177,16 +1173,14 @@ def ray_maps(z_vals, weights, depth, X=None, accumulate=False, normal_col=None, 
     counters (6,) int64 is accumulated into when given (RAY_MAP_COUNTERS names its entries).
     -> surf_idx (R,) int32, surf (R, E) or None, var (R,), std (R,), accum (R, E) or None, counters."""
     name = "ray_maps"
-    _maps_f32(name, z_vals, "z_vals", (None, None))
-    R, S = z_vals.shape
-    _maps_f32(name, weights, "weights", (R, S))
-    _maps_f32(name, depth, "depth", (R,))
+    R, S = _need(name, z_vals, "z_vals", F32, ("R", "S")).shape
+    _need(name, weights, "weights", F32, (R, S))
+    _need(name, depth, "depth", F32, (R,))
     if not 1 <= S <= L.BN_MAPS_MAX_SAMPLES:
         raise ValueError(f"{name}: S = {S} samples (1 to {L.BN_MAPS_MAX_SAMPLES})")
     E = 0
     if X is not None:
-        _maps_f32(name, X, "X", (R, S, None), contiguous=False)
-        E = X.shape[2]
+        E = _need(name, X, "X", F32, (R, S, "E"), False).shape[2]
         if not 0 <= E <= L.BN_MAPS_MAX_CHANNELS:
             raise ValueError(f"{name}: X has E = {E} channels (0 to {L.BN_MAPS_MAX_CHANNELS})")
         if any(st < 0 for st in X.stride()):
@@ -1200,16 +1194,10 @@ def ray_maps(z_vals, weights, depth, X=None, accumulate=False, normal_col=None, 
             raise ValueError(f"{name}: normal column {nc} outside [0, E - 3] with E = {E}")
         if view is None:
             raise ValueError(f"{name}: a normal column needs the view vectors (view = -rays_d)")
-        _maps_f32(name, view, "view", (R, 3), contiguous=False)
-        if view.stride(1) != 1 or view.stride(0) < 0:
-            view = view.contiguous()
-    if counters is None:
-        counters = torch.zeros((len(RAY_MAP_COUNTERS),), dtype=torch.int64, device=z_vals.device)
-    if not (isinstance(counters, torch.Tensor) and counters.dtype == torch.int64 and counters.numel() == len(RAY_MAP_COUNTERS)
-            and counters.is_contiguous()):
-        raise ValueError(f"{name}: counters must be a contiguous int64 tensor of {len(RAY_MAP_COUNTERS)} entries")
-    _fill_device(name, z_vals, weights, depth, counters, *(t for t in (X, view if nc >= 0 else None) if t is not None))
+        view = _need(name, view, "view", F32, (R, 3), "rows")
     dev = z_vals.device
+    counters = _out(name, counters, "counters", I64, (len(RAY_MAP_COUNTERS),), dev, flat=True)
+    _on_device(name, z_vals, weights, depth, counters, X, view if nc >= 0 else None)
     surf_idx = torch.empty((R,), dtype=torch.int32, device=dev)
     var, std = torch.empty((R,), dtype=torch.float32, device=dev), torch.empty((R,), dtype=torch.float32, device=dev)
     surf = torch.empty((R, E), dtype=torch.float32, device=dev) if (E and want_surf) else None
@@ -1226,20 +1214,10 @@ def point_normals(points, valid=None, round_f32=True):
     """The normals of an (H, W, 3) float64 image of points (bn_point_normals): -> normals (H, W, 3) float32, zero on the border, and
     valid_out (H, W) float32 or None (with valid (H, W) float32).  round_f32: the reference's float32 points."""
     name = "point_normals"
-    if not isinstance(points, torch.Tensor):
-        raise ValueError(f"{name}: points must be a tensor on the device (there is no host path)")
-    if points.dtype != torch.float64:
-        raise ValueError(f"{name}: points are {points.dtype}, not torch.float64 (point_cloud's output)")
-    if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] < 1 or points.shape[1] < 1:
-        raise ValueError(f"{name}: points {tuple(points.shape)} are not an (H, W, 3) image")
-    H, W = points.shape[0], points.shape[1]
-    if H * W > 1 << 30:
-        raise ValueError(f"{name}: image {H} x {W} (H W at most 2^30 cells)")
-    if valid is not None:
-        _maps_f32(name, valid, "valid", (H, W), contiguous=False)
-        valid = valid.contiguous()
-    _fill_device(name, points, *(() if valid is None else (valid,)))
-    points = points.contiguous()
+    points = _need(name, points, "the image of points", F64, ("H", "W", 3), "copy", cells=(1, 1 << 30))
+    H, W = points.shape[:2]
+    valid = _maybe(name, valid, "valid", F32, (H, W), "copy")
+    _on_device(name, points, valid)
     out = torch.empty((H, W, 3), dtype=torch.float32, device=points.device)
     valid_out = None if valid is None else torch.empty((H, W), dtype=torch.float32, device=points.device)
     L.check(L.lib().bn_point_normals(_p(points), H, W, int(bool(round_f32)), _p(valid), _p(out), _p(valid_out), _stream()),
@@ -1252,20 +1230,23 @@ def sample_shade_dirs(desc, X, w, rays_d, sun, view=None, rgb=None, brdf=None, w
     w (R,S) their weights; rays_d (R,3) view with unit inner stride; sun (K,3); view (K,3) or None (-rays_d).  rgb / brdf: (K,R,3)
     float32 on the device, rows contiguous - the planes may be further apart (a (K, i:j, 3) slice of a whole view).
     -> rgb (K,R,3) and brdf (K,R,3) = sum_s w brdf_s or None (with `brdf` given or want_brdf)."""
-    R, S, Cc = X.shape
-    K = sun.shape[0]
-    for t in (X, w, sun) + (() if view is None else (view,)):
-        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-    assert w.shape == (R, S) and sun.shape == (K, 3) and (view is None or view.shape == (K, 3)) and desc.C == Cc
-    rdp, rds = _rows3(rays_d, R)
+    name = "sample_shade_dirs"
+    R, S = _need(name, X, "X", F32, ("R", "S", int(desc.C))).shape[:2]
+    _need(name, w, "w", F32, (R, S))
+    K = _need(name, sun, "sun", F32, ("K", 3)).shape[0]
+    _maybe(name, view, "view", F32, (K, 3))
+    rays_d = _need(name, rays_d, "rays_d", F32, (R, 3), "rows")
     if rgb is None:
         rgb = torch.empty((K, R, 3), dtype=torch.float32, device=X.device)
     if brdf is None and want_brdf:
         brdf = torch.empty((K, R, 3), dtype=torch.float32, device=X.device)
     planes = []
-    for t in (rgb, brdf):
-        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.shape == (K, R, 3) and plane_rows(t))
+    for t, what in ((rgb, "rgb"), (brdf, "brdf")):
+        if t is not None and not plane_rows(_need(name, t, what, F32, (K, R, 3), False)):
+            raise ValueError(f"{name}: {what} with strides {t.stride()}: its (R, 3) planes must be contiguous rows that do not overlap")
         planes.append(3 * R if (t is None or K == 1) else t.stride(0))
+    _on_device(name, X, w, sun, view, rays_d, rgb, brdf)
+    rdp, rds = _rows3(rays_d, R)
     raw = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     L.check(L.lib().bn_sample_shade_dirs(C.byref(desc), _p(X), _p(w), rdp, rds, _p(sun), _p(view), R, S, K, raw(rgb), planes[0],
                                          raw(brdf), planes[1], _stream()), "bn_sample_shade_dirs")
@@ -1283,16 +1264,14 @@ def sun_ray_table(rays, d1, sun, u, table=None, z_sun=None):
     contiguous, d1 (R,) the pass-1 depth, sun (K, 3), u (R, G) the pass's uniforms, shared by all K.  -> table (K R, 8) rows
     (surface point, sun_k, 0.01 far, far) and z_sun (K R, G): what field_sigma(rays=table, z=z_sun) takes; per direction bitwise
     rendering.sun_far + stratified_z + the torch.cat of rendering._sample_passes."""
-    R, G = u.shape
-    K = sun.shape[0]
-    for t in (rays, d1, sun, u):
-        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-    assert rays.dim() == 2 and rays.shape[0] == R and rays.shape[1] >= 6 and d1.numel() == R and sun.shape == (K, 3)
-    if table is None:
-        table = torch.empty((K * R, 8), dtype=torch.float32, device=u.device)
-    if z_sun is None:
-        z_sun = torch.empty((K * R, G), dtype=torch.float32, device=u.device)
-    assert table.shape == (K * R, 8) and z_sun.shape == (K * R, G)
+    name = "sun_ray_table"
+    R, G = _need(name, u, "u", F32, ("R", "G")).shape
+    _need(name, rays, "rays", F32, (R, ">=6"))
+    _need(name, d1, "d1", F32, R)
+    K = _need(name, sun, "sun", F32, ("K", 3)).shape[0]
+    table = _out(name, table, "table", F32, (K * R, 8), u.device, torch.empty)
+    z_sun = _out(name, z_sun, "z_sun", F32, (K * R, G), u.device, torch.empty)
+    _on_device(name, u, rays, d1, sun, table, z_sun)
     L.check(L.lib().bn_sun_ray_table(_p(rays), rays.shape[1], _p(d1), _p(sun), _p(u), R, K, G, _p(table), _p(z_sun), _stream()),
             "bn_sun_ray_table")
     return table, z_sun
@@ -1305,24 +1284,31 @@ def sun_shade_dirs(desc, sigma_sun, z_sun, rays_d, sun, acc=None, wsum=None, X=N
     BRDF per ray - or X (R, G, C), w (R, G) - per-sample shading; rays_d (R, 3) view with unit inner stride; sun (K, 3).  rgb (K, R, 3)
     / vis (K, R): float32 on the device, rows contiguous - the planes may be further apart (a (K, i:j) slice of a whole view).
     -> rgb (K, R, 3) and vis (K, R) = T_{G-1} or None (with `vis` given or want_vis)."""
-    K = sun.shape[0]
-    R = (acc if acc is not None else X).shape[0] if (acc is not None or X is not None) else sigma_sun.numel() // max(1, K)
+    name = "sun_shade_dirs"
+    K = _need(name, sun, "sun", F32, ("K", 3)).shape[0]
+    src = acc if acc is not None else X
+    _need(name, sigma_sun, "sigma_sun", F32)
+    R = src.shape[0] if isinstance(src, torch.Tensor) and src.dim() else sigma_sun.numel() // max(1, K)
     G = sigma_sun.numel() // max(1, K * R)
     dev = sigma_sun.device
-    for t in (sigma_sun, z_sun, sun, acc, wsum, X, w, noise):
-        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous())
-    assert sigma_sun.numel() == K * R * G == z_sun.numel() and sun.shape == (K, 3)
-    assert noise is None or noise.shape == (R, G)
-    assert acc is None or (acc.shape == (R, desc.C) and wsum is not None and wsum.numel() == R)
-    assert X is None or (X.shape == (R, G, desc.C) and w is not None and w.shape == (R, G))
-    rdp, rds = _rows3(rays_d, R)
+    _need(name, sigma_sun, "sigma_sun", F32, K * R * G)
+    _need(name, z_sun, "z_sun", F32, K * R * G)
+    _maybe(name, noise, "noise", F32, (R, G))
+    _maybe(name, acc, "acc", F32, (R, int(desc.C)))
+    (_maybe if acc is None else _need)(name, wsum, "wsum", F32, R)                     # acc needs its wsum, X its w
+    _maybe(name, X, "X", F32, (R, G, int(desc.C)))
+    (_maybe if X is None else _need)(name, w, "w", F32, (R, G))
+    rays_d = _need(name, rays_d, "rays_d", F32, (R, 3), "rows")
     if rgb is None:
         rgb = torch.empty((K, R, 3), dtype=torch.float32, device=dev)
     if vis is None and want_vis:
         vis = torch.empty((K, R), dtype=torch.float32, device=dev)
-    assert rgb.is_cuda and rgb.dtype == torch.float32 and rgb.shape == (K, R, 3) and plane_rows(rgb)
-    assert vis is None or (vis.is_cuda and vis.dtype == torch.float32 and vis.shape == (K, R) and (R == 1 or vis.stride(1) == 1)
-                           and (K == 1 or vis.stride(0) >= R))
+    if not plane_rows(_need(name, rgb, "rgb", F32, (K, R, 3), False)):
+        raise ValueError(f"{name}: rgb with strides {rgb.stride()}: its (R, 3) planes must be contiguous rows that do not overlap")
+    if _maybe(name, vis, "vis", F32, (K, R), False) is not None and (R > 1 and vis.stride(1) != 1 or K > 1 and vis.stride(0) < R):
+        raise ValueError(f"{name}: vis with strides {vis.stride()}: its rows must be contiguous and must not overlap")
+    _on_device(name, sigma_sun, z_sun, sun, acc, wsum, X, w, noise, rays_d, rgb, vis)
+    rdp, rds = _rows3(rays_d, R)
     raw = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     L.check(L.lib().bn_sun_shade_dirs(C.byref(desc), _p(sigma_sun), _p(z_sun), _p(noise), float(noise_std), _p(acc), _p(wsum), _p(X),
                                       _p(w), rdp, rds, _p(sun), R, G, K, raw(rgb), 3 * R if K == 1 else rgb.stride(0), raw(vis),

@@ -23,7 +23,7 @@ maps (cv2 / PIL), TensorBoard, GeoTIFF I/O, the `sun` map, visu_scale != 1.
 import torch
 
 from . import functions as Fn
-from .functions import RAY_MAP_COUNTERS
+from .functions import RAY_MAP_COUNTERS, fixed_mean
 
 _PRECISIONS = {"reference": True, "exact": False}
 STD_FIX = 2.0 ** 20
@@ -215,7 +215,7 @@ def view_maps(models, args, rays, H, W, frame=None, chunk=None, apply_brdf=False
     n_lr = int(host[1, 5])
     pct = lambda k, n: 100.0 * k / n if n else None
     result["counters"] = {"an": host[0], "lr": host[1], "main": main_row}
-    result["stats"] = {"depth_std": int(c[0]) / (int(c[1]) * STD_FIX) if int(c[1]) else float("nan"), "depth_std_skipped": int(c[2]),
+    result["stats"] = {"depth_std": fixed_mean(int(c[0]), int(c[1]), STD_FIX), "depth_std_skipped": int(c[2]),
                        "bad_nr_an%": pct(int(host[0, 3]), n_an), "nr_an0%": pct(int(host[0, 4]), n_an),
                        "bad_nr_lr%": pct(int(host[1, 3]), n_lr)}
     if frame is not None:

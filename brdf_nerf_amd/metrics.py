@@ -118,11 +118,6 @@ def _ssim_sums(rgb, target, H, W, mask, window, layout, scl, rows, want_map):
     return sums, maps, max_val
 
 
-def _ssim_value(triple):
-    s, n, _ = (int(v) for v in triple)
-    return s / (n * SSIM_FIX) if n else float("nan")
-
-
 @torch.no_grad()
 def image_ssim(rgb, target, H, W, mask=None, window=3, layout="reference", scl=False, rows=None, want_map=False):
     """metrics.py:327-341 as eval.py:471 calls it: the mean of the SSIM index map of the two masked images, Gaussian window
@@ -138,8 +133,9 @@ def image_ssim(rgb, target, H, W, mask=None, window=3, layout="reference", scl=F
     A cell whose index is not finite is left out of the mean and counted in `skipped` (upstream's mean would be NaN)."""
     sums, maps, max_val = _ssim_sums(rgb, target, H, W, mask, window, layout, scl, rows, want_map)
     host = sums.cpu()
+    ssim, ssim_scl = (Fn.fixed_mean(s, n, SSIM_FIX) for s, n, _ in host.tolist())
     info = {"skipped": int(host[0, 2]), "sums": host, "max_val": max_val, "map": maps[0], "map_scl": maps[1]}
-    return _ssim_value(host[0]), (_ssim_value(host[1]) if scl else -1), info
+    return ssim, (ssim_scl if scl else -1), info
 
 
 @torch.no_grad()
@@ -154,10 +150,6 @@ def dsm_normals(dsm, resolution):
     if not (resolution > 0 and math.isfinite(resolution)):
         raise ValueError(f"dsm_normals: resolution {resolution} must be positive")
     return Fn.grid_normals(Fn._f32(dsm), resolution)
-
-
-def _angle_value(s, n):
-    return int(s) / (int(n) * ANGLE_FIX) if int(n) else float("nan")
 
 
 @torch.no_grad()
@@ -181,9 +173,9 @@ def normal_angle_mae(dsm, gt, resolution, mask=None, border="reference"):
     angle, sums = Fn.normal_angle(dsm_normals(dsm, resolution), dsm_normals(gt, resolution), _mask_hw(mask, H, W, dsm.device),
                                   _BORDERS[border])
     s = sums.cpu()
-    return {"mae_nr": _angle_value(s[0], s[1]), "diff_nr": angle, "sums": s,
-            "mae_nr_in": _angle_value(s[2], s[3]) if mask is not None else -1,
-            "mae_nr_out": _angle_value(s[4], s[5]) if mask is not None else -1}
+    mean = [Fn.fixed_mean(t, n, ANGLE_FIX) for t, n in s.reshape(3, 2).tolist()]            # all, inside, outside
+    return {"mae_nr": mean[0], "diff_nr": angle, "sums": s, "mae_nr_in": mean[1] if mask is not None else -1,
+            "mae_nr_out": mean[2] if mask is not None else -1}
 
 
 @torch.no_grad()
@@ -241,7 +233,8 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
     res["psnr"], res["psnr_scl"] = float(p), float(p_scl)
     sums, _, _ = _ssim_sums(rgb, rgbs, H, W, mask, window, layout, True, row_band("score_view", H, None, group), False)
     host = allreduce_(sums, group=group).cpu()
-    res.update(ssim=_ssim_value(host[0]), ssim_scl=_ssim_value(host[1]), ssim_skipped=int(host[0, 2]), ssim_sums=host)
+    ssim, ssim_scl = (Fn.fixed_mean(s, n, SSIM_FIX) for s, n, _ in host.tolist())
+    res.update(ssim=ssim, ssim_scl=ssim_scl, ssim_skipped=int(host[0, 2]), ssim_sums=host)
     if frame is not None:
         walk = ViewWalk(rays.shape[0], render_kw.get("chunk") or args.chunk, group)     # render_image's: the rays this rank rendered
         if grid is None:

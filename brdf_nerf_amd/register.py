@@ -137,10 +137,6 @@ def register_xy(dsm, gt, irange=5, min_size=100, rows=None, group=None):
     return {"dx": dx, "dy": dy, "b": b, "k": k, "pivot": pivot, "levels": levels, "moments": moments, "skipped": int(skipped.item())}
 
 
-def _mae(s, n):
-    return int(s) / (int(n) * MAE_FIX) if int(n) else float("nan")
-
-
 @torch.no_grad()
 def apply_registration(dsm, gt, dx, dy, b, mask=None):
     """dsmr.apply_shift and the difference of sat_utils.py:246: rdsm[j][i] = (float)(dsm[j + dy][i + dx] + b), NaN where that cell
@@ -160,9 +156,10 @@ def apply_registration(dsm, gt, dx, dy, b, mask=None):
         raise ValueError(f"apply_registration: mask of {torch.as_tensor(mask).numel()} cells for a grid of {H} x {W}")
     rdsm, diff, sums = Fn.dsm_shift_diff(Fn._f32(pred), Fn._f32(gt), dx, dy, b, _mask_hw(mask, H, W, pred.device))
     s = sums.cpu()
-    res = {"rdsm": rdsm, "diff": diff, "mae": _mae(s[0], s[1]), "sums": s}
+    mean = [Fn.fixed_mean(t, n, MAE_FIX) for t, n in s.reshape(3, 2).tolist()]              # all, inside, outside
+    res = {"rdsm": rdsm, "diff": diff, "mae": mean[0], "sums": s}
     if mask is not None:
-        res.update(mae_in=_mae(s[2], s[3]), mae_out=_mae(s[4], s[5]))
+        res.update(mae_in=mean[1], mae_out=mean[2])
     return res
 
 

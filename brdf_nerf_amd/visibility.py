@@ -68,7 +68,7 @@ def grid_visibility(dsm, resolution, dirs, eps=0.0, rows=None, group=None, want_
     nodata)} (+ "hit" (K, H, W) int32: the flat index of the first blocking cell, or -1)."""
     from .distributed import allreduce_, gather_rows, row_band, world_info
     name = "grid_visibility"
-    Fn._vis_grid(name, dsm)
+    Fn._need(name, dsm, **Fn.VIS_DSM)
     dirs = Fn._vis_dirs(name, dirs)
     H, W = dsm.shape
     K = dirs.shape[0]
@@ -78,7 +78,7 @@ def grid_visibility(dsm, resolution, dirs, eps=0.0, rows=None, group=None, want_
     if step < 1:
         raise ValueError(f"{name}: dir_tile {dir_tile} must be at least 1")
     Fn._vis_scalars(name, resolution, eps, 0.0)
-    Fn._fill_device(name, dsm)
+    Fn._on_device(name, dsm)
     zmax = _zmax(dsm)
     alone = world == 1 and rows != (0, H)                  # a band without a group: the other rows are NODATA and -1
     buffer = lambda dtype, value: torch.full((K, H, W), value, dtype=dtype, device=dsm.device) if alone else \
@@ -103,7 +103,7 @@ def grid_visibility(dsm, resolution, dirs, eps=0.0, rows=None, group=None, want_
 
 
 def _on_grid(name, dsm, grid):
-    Fn._vis_grid(name, dsm)
+    Fn._need(name, dsm, **Fn.VIS_DSM)
     if tuple(dsm.shape) != (grid.height, grid.width):
         raise ValueError(f"{name}: dsm {tuple(dsm.shape)} is not on the grid of {grid.height} x {grid.width} cells")
 
@@ -115,10 +115,10 @@ def point_visibility(points, dsm, grid, dirs, eps=0.0, want_hit=False):
     not over the grid, is NODATA.
     -> {"visible" (K, R) uint8, "counts" (K, 3) int64 on the host} (+ "hit" (K, R) int32)."""
     name = "point_visibility"
-    Fn._vis_points(name, points)
+    Fn._need(name, points, **Fn.VIS_POINTS)
     _on_grid(name, dsm, grid)
     Fn._vis_dirs(name, dirs)
-    Fn._fill_device(name, points, dsm)
+    Fn._on_device(name, points, dsm)
     vis, hit, counts = Fn.points_visibility(points, dsm, grid.xoff, grid.yoff, grid.resolution, dirs, eps, _zmax(dsm), want_hit=want_hit)
     return _result(vis, hit, counts, want_hit)
 

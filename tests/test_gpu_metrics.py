@@ -210,6 +210,43 @@ def test_normal_angle_against_the_statement(name):
     assert sums2 == sums and np.array_equal(bits(again), bits(got))
 
 
+EDGE_GRIDS = [(1, 1), (1, 63), (1, 64), (1, 65), (1, 255), (16, 16), (1, 257), (3, 171)]      # one cell; a wave, a block +- one cell
+EDGE_MASKS = ("none", "zero", "one", "odd")
+
+
+def edge_mask(kind, H, W):
+    """(H, W) uint8 numpy or None: no mask, all zero, all one, or the cells of odd index."""
+    odd = (np.arange(H * W).reshape(H, W) & 1).astype(np.uint8)
+    return {"none": None, "zero": odd * 0, "one": odd * 0 + 1, "odd": odd}[kind]
+
+
+@pytest.mark.parametrize("mask_kind", EDGE_MASKS)
+@pytest.mark.parametrize("H,W,border", [g + (0,) for g in EDGE_GRIDS] + [(3, 171, 1)])
+def test_normal_angle_sums_at_lane_wave_and_block_edges(H, W, border, mask_kind):
+    """The six block sums where the other cases never go: one cell, a last wave and a last block that are full, one short or one
+    over.  n1 cycles through (0,0,1), (1,0,0), (0,0,-1), (0,1,0) by cell index against n2 = (0,0,1): every angle is 0, 90 or 180
+    degrees, arccos is exact there, so the sums equal the statement's AND the closed form (90 n90 + 180 n180) 2^20 exactly."""
+    from brdf_nerf_amd import functions as Fn
+    cell = np.arange(H * W).reshape(H, W)
+    n1 = np.float32([(0, 0, 1), (1, 0, 0), (0, 0, -1), (0, 1, 0)])[cell % 4]
+    n2 = np.broadcast_to(np.float32([0, 0, 1]), (H, W, 3))
+    mask = edge_mask(mask_kind, H, W)
+    _, sums = Fn.normal_angle(dev(n1), dev(n2), None if mask is None else dev(mask), border, want_map=False)
+    sums = [int(v) for v in sums.cpu()]
+    want = M.angle_map(n1, n2, border)
+    counted = ~np.isnan(want)
+    inside = np.ones((H, W), bool) if mask is None else mask != 0
+    closed = []
+    for sel in (counted, counted & inside, counted & ~inside):
+        n90, n180 = int((sel & (cell % 2 == 1)).sum()), int((sel & (cell % 4 == 2)).sum())
+        closed += [(90 * n90 + 180 * n180) << 20, int(sel.sum())]
+    print(f"ANGLE EDGE {H}x{W} border {border} mask {mask_kind}: sums {sums} statement {M.angle_sums(want, mask)} closed form {closed}")
+    assert sums == M.angle_sums(want, mask)
+    assert sums == closed
+    if border:
+        assert sums[1] == 169
+
+
 def test_normal_angle_mae_is_its_sums():
     from brdf_nerf_amd import normal_angle_mae
     (res, z1), (_, z2) = M.normal_case("33x31"), M.normal_case("33x31_other")

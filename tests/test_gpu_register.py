@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import register_cases as R
+from test_gpu_metrics import EDGE_GRIDS, EDGE_MASKS, edge_mask
 from test_gpu_parity import DEV, _free_port
 from test_register_cpu import bits32, bits64
 
@@ -90,6 +91,23 @@ def test_dsm_shift_diff_bit_equal_to_the_statement(name):
         assert sums == [0] * 6 and bool(torch.isnan(rdsm).all())
     none, none2, again = Fn.dsm_shift_diff(dev(c["pred"]), dev(c["gt"]), c["dx"], c["dy"], c["b"], mask, want_maps=False)
     assert none is None and none2 is None and [int(x) for x in again.cpu()] == sums_w
+
+
+@pytest.mark.parametrize("mask_kind", EDGE_MASKS)
+@pytest.mark.parametrize("H,W", EDGE_GRIDS)
+def test_dsm_shift_diff_at_lane_wave_and_block_edges(H, W, mask_kind):
+    """The six block sums where R.SHIFT_CASES never go (one cell; a last wave and a last block that are full, one short or one
+    over; a mask that is all zero, all one or every other cell): rdsm, diff and the sums equal the statement's bit for bit."""
+    from brdf_nerf_amd import functions as Fn
+    pred, gt = R._grid(H, W, 5 + W, nan=0.1).astype(np.float32), R._grid(H, W, 6 + W, nan=0.1).astype(np.float32)
+    mask = edge_mask(mask_kind, H, W)
+    rdsm_w, diff_w, sums_w = R.shift_diff(pred, gt, 0, 0, 0.5, mask)
+    rdsm, diff, sums = Fn.dsm_shift_diff(dev(pred), dev(gt), 0, 0, 0.5, None if mask is None else dev(mask))
+    sums = [int(x) for x in sums.cpu()]
+    print(f"SHIFT EDGE {H}x{W} mask {mask_kind}: sums {sums} (statement {sums_w}), NaN cells {int(np.isnan(diff_w).sum())} of {diff_w.size}")
+    assert np.array_equal(bits32(rdsm.cpu().numpy()), bits32(rdsm_w))
+    assert np.array_equal(bits32(diff.cpu().numpy()), bits32(diff_w))
+    assert sums == sums_w
 
 
 @pytest.mark.parametrize("name", R.GOLDENS)

@@ -458,3 +458,76 @@ def test_ray_table_staging_buffers_keep_their_addresses():
         parts.append(c.next_batch(100, rank=r, world=3, out=c.staging(34))["rgbs"].clone())
         offs.append(c.last_offset)
     assert offs == [0, 34, 67] and torch.equal(torch.cat(parts), a.next_batch(100)["rgbs"])
+
+
+def _evaluation_calls():
+    """Every wrapper of functions.py that runs after training -> name: (function, valid arguments on the HOST, the index of one
+    tensor among them, the name of that tensor's dtype)."""
+    from types import SimpleNamespace
+    from brdf_nerf_amd import functions as Fn
+    f32, f64, i32, i64 = torch.float32, torch.float64, torch.int32, torch.int64
+    z = lambda *shape, dtype=f32: torch.zeros(shape, dtype=dtype)
+    R, S, K, E, H, W = 4, 8, 2, 3, 3, 5
+    rays, depth, one = z(R, 8), z(R), z(1, dtype=i64)
+    frame, grid, world = ((0.0, 0.0, 0.0), 1.0), (0.0, 0.0, 0.5, 1, 0), (0, 17, 0)
+    desc = SimpleNamespace(C=7)
+    return {
+        "dsm_splat": (Fn.dsm_splat, [rays, depth, *frame, *grid, z(H, W, 2, dtype=i64), one], 0, "float32"),
+        "ecef_geodetic": (Fn.ecef_geodetic, [z(R, 3, dtype=f64), one], 0, "float64"),
+        "surface_points": (Fn.surface_points, [rays, depth, *frame, *world, one], 1, "float32"),
+        "dsm_splat_points": (Fn.dsm_splat_points, [z(R, 3, dtype=f64), *grid, z(H, W, 2, dtype=i64), one], 0, "float64"),
+        "dsm_splat_world": (Fn.dsm_splat_world, [rays, depth, *frame, *grid, *world, z(H, W, 2, dtype=i64), one], 12, "int64"),
+        "ortho_top": (Fn.ortho_top, [rays, depth, *frame, *grid, *world, z(H, W, dtype=i64), one], 12, "int64"),
+        "ortho_splat": (Fn.ortho_splat, [rays, depth, *frame, *grid, *world, z(R, E), z(H, W, dtype=i64), 0, z(H, W, 2 + E, dtype=i64),
+                                         z(3, dtype=i64)], 12, "float32"),
+        "ortho_resolve": (Fn.ortho_resolve, [z(H, W, 2 + E, dtype=i64)], 0, "int64"),
+        "dsm_resolve": (Fn.dsm_resolve, [z(H, W, 2, dtype=i64)], 0, "int64"),
+        "ssim_map": (Fn.ssim_map, [z(3 * H * W), z(3 * H * W), 3, H, W, (H * W, W, 1), None, 1.0, 1.0, 3, [0.25, 0.5, 0.25],
+                                   z(3, dtype=i64)], 1, "float32"),
+        "grid_normals": (Fn.grid_normals, [z(H, W), 0.5], 0, "float32"),
+        "normal_angle": (Fn.normal_angle, [z(H, W, 3), z(H, W, 3)], 1, "float32"),
+        "grid_halve": (Fn.grid_halve, [z(H, W, dtype=f64)], 0, "float64"),
+        "ncc_moments": (Fn.ncc_moments, [z(H, W, dtype=f64), z(H, W, dtype=f64), 0.0, 10, 0, 0, 1], 1, "float64"),
+        "dsm_shift_diff": (Fn.dsm_shift_diff, [z(H, W), z(H, W), 0, 0, 0.5], 0, "float32"),
+        "grid_nearest_col": (Fn.grid_nearest_col, [z(H, W)], 0, "float32"),
+        "grid_fill": (Fn.grid_fill, [z(H, W), z(H, W, dtype=i32)], 1, "int32"),
+        "grid_visibility": (Fn.grid_visibility, [z(H, W), 0.5, [0.0, 0.0, 1.0]], 0, "float32"),
+        "points_visibility": (Fn.points_visibility, [z(R, 3, dtype=f64), z(H, W), 0.0, 0.0, 0.5, [0.0, 0.0, 1.0]], 0, "float64"),
+        "ray_maps": (Fn.ray_maps, [z(R, S), z(R, S), z(R)], 2, "float32"),
+        "point_normals": (Fn.point_normals, [z(H, W, 3, dtype=f64)], 0, "float64"),
+        "sample_shade_dirs": (Fn.sample_shade_dirs, [desc, z(R, S, 7), z(R, S), z(R, 3), z(K, 3)], 2, "float32"),
+        "sun_ray_table": (Fn.sun_ray_table, [rays, z(R), z(K, 3), z(R, S)], 1, "float32"),
+        "sun_shade_dirs": (Fn.sun_shade_dirs, [desc, z(K, R, S), z(K, R, S), z(R, 3), z(K, 3), z(R, 7), z(R)], 2, "float32"),
+    }
+
+
+def test_evaluation_wrappers_refuse_by_name(monkeypatch):
+    """Every evaluation wrapper hands raw pointers to the library, so each refuses a host tensor ("device", after every other
+    check) and a wrong dtype (by the name of the right one) with ValueError before the library is loaded - also under python -O,
+    where an assert would be gone: a fresh child process sees the same refusal from a wrapper that used to assert."""
+    import inspect
+    from brdf_nerf_amd import _lib
+    from brdf_nerf_amd import functions as Fn
+
+    def trap(*a, **k):
+        raise AssertionError("the library was called")
+    monkeypatch.setattr(_lib, "lib", trap)
+    calls = _evaluation_calls()
+    src = inspect.getsource(Fn)
+    body = src[src.index("def dsm_splat("):src.index("def sample_brdf(")]
+    in_scope = [n for n in re.findall(r"^def ([a-z]\w*)\(", body, re.M) if "L.lib()" in inspect.getsource(getattr(Fn, n))]
+    assert sorted(in_scope) == sorted(calls), "the table names every wrapper from dsm_splat to sun_shade_dirs"
+    other = {torch.float32: torch.float64, torch.float64: torch.float32, torch.int64: torch.int32, torch.int32: torch.int64}
+    for name, (fn, args, at, dtype) in calls.items():
+        with pytest.raises(ValueError, match="device"):
+            fn(*args)
+        assert str(args[at].dtype) == "torch." + dtype, name
+        wrong = list(args)
+        wrong[at] = args[at].to(other[args[at].dtype])
+        with pytest.raises(ValueError, match=rf"^{name}: .*{dtype}"):
+            fn(*wrong)
+    code = ("import torch\nfrom brdf_nerf_amd import functions as Fn\nif __debug__:\n    raise SystemExit('asserts are on')\n"
+            "try:\n    Fn.dsm_shift_diff(torch.zeros(3, 5, dtype=torch.float64), torch.zeros(3, 5), 0, 0, 0.5)\n"
+            "except ValueError as e:\n    print('refused:', e)\n")
+    out = subprocess.run([sys.executable, "-O", "-c", code], cwd=ROOT, text=True, capture_output=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.startswith("refused: dsm_shift_diff: pred") and "float32" in out.stdout, out.stdout + out.stderr
