@@ -68,11 +68,12 @@ _TRACKERS = ("-mllvm", "-amdgpu-use-amdgpu-trackers=1") + _NOSLP
 # statement bit for bit, for the same reason; register.hip: the box means of the pyramid and the quanta of the altitudes likewise;
 # view_maps.hip: the serial float64 sums per ray and the shared normal chain likewise; camera.hip: the RPC polynomials and the Newton
 # steps of the localisation likewise; ortho.hip: world.hip's chain (surface_cell.h) and the quanta of the feature channels;
-# visibility.hip: the march's u0 + t su, v0 + t sv, z0 + t sz and zt + eps (a contracted multiply-add moves a step across a cell edge).
+# visibility.hip: the march's u0 + t su, v0 + t sv, z0 + t sz and zt + eps (a contracted multiply-add moves a step across a cell edge);
+# orthophoto.hip: camera.hip's polynomials (rpc_poly.h) after the inverse UTM, and the bilinear taps, held to a statement bit for bit.
 FILE_FLAGS = {"field_wgrad.hip": ("-mllvm", "-amdgpu-sched-strategy=max-ilp"), "world.hip": ("-ffp-contract=off",),
               "metrics.hip": ("-ffp-contract=off",), "register.hip": ("-ffp-contract=off",), "view_maps.hip": ("-ffp-contract=off",),
               "camera.hip": ("-ffp-contract=off",), "ortho.hip": ("-ffp-contract=off",), "visibility.hip": ("-ffp-contract=off",),
-              "field_fwd.hip": _NOSLP,
+              "orthophoto.hip": ("-ffp-contract=off",), "field_fwd.hip": _NOSLP,
               "field_bwd.hip": _TRACKERS, "field_adjoint.hip": _TRACKERS, "field_adjbwd.hip": _TRACKERS}
 
 

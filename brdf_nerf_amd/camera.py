@@ -28,7 +28,10 @@ a dsm.SceneFrame given in place of center and range must state the same one (its
 a parameter of the scene, not taken from the first pixel of each call as upstream does (sat_utils.py:156-159); south=False adds
 no false northing, which is what upstream's "+proj=utm +zone=17R" does in both hemispheres.
 
-Not here: the file readers (JSON, GeoTIFF, the tie-point text files), image scaling, an inverse UTM, a `group` for depth_priors
+  utm_geodetic       UTM points -> geodetic points (Karney's inverse series and Newton for the latitude) (bn_utm_geodetic)
+  view_direction     the direction from the surface towards the sensor at one pixel, in (east, north, up)
+
+Not here: the file readers (JSON, GeoTIFF, the tie-point text files), image scaling, a `group` for depth_priors
 (a view's priors are made once), the normals as a table column.
 The RPC rule is the public RPC00B definition and the UTM series Karney's; neither was checked against rpcm or pyproj.
 """
@@ -232,6 +235,41 @@ def ecef_geodetic(xyz, device=None, want_skipped=False):
     skipped = torch.zeros((1,), dtype=torch.int64, device=dev)
     lonlat, alt = Fn.ecef_geodetic(xyz, skipped)
     return (lonlat, alt, int(skipped.item())) if want_skipped else (lonlat, alt)
+
+
+@torch.no_grad()
+def utm_geodetic(en, zone, south=False, device=None):
+    """Geodetic points of UTM points ("Orthophoto of an observed image" in the header, step 2; the counterpart of
+    geo_world(cs='utm')): en (n, 2) metres = (east, north) in `zone`, south=True taking the false northing off -> lonlat float64
+    (n, 2) in degrees (NaN where lon or lat is not finite), skipped (their number)."""
+    from . import functions as Fn
+    dev = _device(device, en)
+    en = torch.as_tensor(en, dtype=torch.float64).to(dev)
+    if en.dim() != 2 or en.shape[1] != 2:
+        raise ValueError(f"utm_geodetic: en must be (n, 2), got {tuple(en.shape)}")
+    _check_count(en.shape[0], "utm_geodetic")
+    skipped = torch.zeros((1,), dtype=torch.int64, device=dev)
+    lonlat = Fn.utm_geodetic(en, zone, south, skipped)
+    return lonlat, int(skipped.item())
+
+
+@torch.no_grad()
+def view_direction(rpc, zone, south, alt_lo, alt_hi, col=None, row=None, device=None):
+    """The direction from the surface towards the sensor at one pixel of a view, in (east, north, up) - what grid_visibility
+    takes: the pixel (default: the image's col_offset, row_offset) localised at alt_lo and at alt_hi, both points taken to the UTM
+    `zone`, P(alt_hi) - P(alt_lo).  Existing entries only (localize, geo_world).  -> float64 (3,) on the host, not normalised."""
+    alt_lo, alt_hi = float(alt_lo), float(alt_hi)
+    if not (math.isfinite(alt_lo) and math.isfinite(alt_hi) and alt_hi > alt_lo):
+        raise ValueError(f"view_direction: altitudes [{alt_lo}, {alt_hi}] must be finite and alt_hi above alt_lo")
+    _world_args("utm", zone, south)
+    col = rpc.col_offset if col is None else float(col)
+    row = rpc.row_offset if row is None else float(row)
+    dev = _device(device)
+    pts = [geo_world(localize(rpc, [col], [row], a, device=dev)[0], a, "utm", zone, south, device=dev) for a in (alt_lo, alt_hi)]
+    d = (pts[1] - pts[0]).reshape(3).cpu()
+    if not bool(torch.isfinite(d).all()):
+        raise ValueError(f"view_direction: pixel ({col}, {row}) does not localise at [{alt_lo}, {alt_hi}]")
+    return d
 
 
 def _frame(center, range, cs):
@@ -557,5 +595,6 @@ def ray_table(views, images, center, range=None, cs="utm", zone=None, south=Fals
     return RayTable(rays, rgbs, **{k: torch.cat(v, 0) for k, v in cols.items()}, device=rays.device, seed=seed)
 
 
-__all__ = ["Rpc", "utm_zone", "sun_direction", "project", "localize", "geo_world", "ecef_geodetic", "view_rays", "scene_bounds",
+__all__ = ["Rpc", "utm_zone", "sun_direction", "project", "localize", "geo_world", "ecef_geodetic", "utm_geodetic", "view_direction",
+           "view_rays", "scene_bounds",
            "ray_table", "nearest_lines", "tie_priors", "depth_priors"]

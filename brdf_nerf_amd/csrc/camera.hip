@@ -36,6 +36,7 @@
 #include "brdfnerf_hip.h"
 #include "block_sums.h"
 #include "geodesy.h"
+#include "rpc_poly.h"
 // every float64 operation below is rounded on its own (see above); the build also passes -ffp-contract=off for this file
 #pragma clang fp contract(off)
 
@@ -43,30 +44,10 @@ namespace {
 
 // UtmK, World, geo_world and make_world: geodesy.h, shared with world.hip
 using namespace geodesy;
+// Mono, monomials, poly, project and rpc_ok: rpc_poly.h, shared with orthophoto.hip
+using namespace rpc_poly;
 
 constexpr int CAM_BLOCK = 256;
-
-struct Mono {
-  double L, P, H, m4, m5, m6, m7, m8, m9, m10, m11, m12, m13, m14, m15, m16, m17, m18, m19;
-};
-
-__device__ __forceinline__ Mono monomials(double L, double P, double H) {
-  Mono m;
-  m.L = L; m.P = P; m.H = H;
-  m.m4 = L * P; m.m5 = L * H; m.m6 = P * H; m.m7 = L * L; m.m8 = P * P; m.m9 = H * H;
-  m.m10 = (P * L) * H; m.m11 = m.m7 * L; m.m12 = m.m4 * P; m.m13 = m.m5 * H; m.m14 = m.m7 * P; m.m15 = m.m8 * P;
-  m.m16 = m.m6 * H; m.m17 = m.m7 * H; m.m18 = m.m8 * H; m.m19 = m.m9 * H;
-  return m;
-}
-
-__device__ __forceinline__ double poly(const double *c, const Mono &m) {
-  double s = c[0];
-  s = s + c[1] * m.L; s = s + c[2] * m.P; s = s + c[3] * m.H; s = s + c[4] * m.m4; s = s + c[5] * m.m5; s = s + c[6] * m.m6;
-  s = s + c[7] * m.m7; s = s + c[8] * m.m8; s = s + c[9] * m.m9; s = s + c[10] * m.m10; s = s + c[11] * m.m11;
-  s = s + c[12] * m.m12; s = s + c[13] * m.m13; s = s + c[14] * m.m14; s = s + c[15] * m.m15; s = s + c[16] * m.m16;
-  s = s + c[17] * m.m17; s = s + c[18] * m.m18; s = s + c[19] * m.m19;
-  return s;
-}
 
 // value and d / dL, d / dP of one polynomial (the derivative table of the header)
 __device__ __forceinline__ void poly_d(const double *c, const Mono &m, double &v, double &dL, double &dP) {
@@ -137,11 +118,10 @@ void rpc_project_kernel(const bn_rpc R, const double *__restrict__ lon, const do
                         const double *__restrict__ alt, int64_t n, double *__restrict__ col, double *__restrict__ row) {
   const int64_t i = (int64_t)blockIdx.x * CAM_BLOCK + threadIdx.x;
   if (i >= n) return;
-  const double L = (lon[i] - R.lon_offset) / R.lon_scale, P = (lat[i] - R.lat_offset) / R.lat_scale;
-  const double H = (alt[i] - R.alt_offset) / R.alt_scale;
-  const Mono m = monomials(L, P, H);
-  col[i] = (poly(R.col_num, m) / poly(R.col_den, m)) * R.col_scale + R.col_offset;
-  row[i] = (poly(R.row_num, m) / poly(R.row_den, m)) * R.row_scale + R.row_offset;
+  double c, r;
+  project(R, lon[i], lat[i], alt[i], c, r);
+  col[i] = c;
+  row[i] = r;
 }
 
 __global__ __launch_bounds__(CAM_BLOCK)
@@ -343,15 +323,6 @@ void tie_priors_kernel(const bn_rpc R, const World Wd, const TieArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-bool rpc_ok(const bn_rpc *rpc) {
-  const double *v = &rpc->row_offset;
-  for (int i = 0; i < 90; ++i)
-    if (!std::isfinite(v[i])) return false;
-  for (int i = 5; i < 10; ++i)
-    if (v[i] == 0.0) return false;
-  return true;
-}
-
 constexpr int64_t CAM_MAX_RAYS = (int64_t)1 << 30;
 
 }  // namespace

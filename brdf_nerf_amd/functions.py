@@ -1474,3 +1474,93 @@ def count_nonfinite(x, counts=None):
     if x.numel():
         L.check(L.lib().bn_count_nonfinite(_p(x), x.numel(), _p(counts), _stream()), "bn_count_nonfinite")
     return counts
+
+
+# ------------------------------------------------------------------------------ the orthophoto entries
+def _zone(name, zone, south):
+    """(zone, south) as the entries take them: an integer zone from 1 to 60 (numpy integers included), south 0 or 1."""
+    try:
+        z = int(zone)
+    except (TypeError, ValueError):
+        z = 0
+    if isinstance(zone, bool) or z != zone or not 1 <= z <= 60:
+        raise ValueError(f"{name}: zone {zone!r} is not an integer from 1 to 60")
+    return z, int(bool(south))
+
+
+def utm_geodetic(en, zone, south, skipped):
+    """Geodetic points of UTM points (bn_utm_geodetic): en (n, 2) float64 = (east, north) in `zone` -> lonlat (n, 2) float64 in
+    degrees, NaN where a point is refused; skipped (1,) int64 on the device, accumulated into."""
+    name = "utm_geodetic"
+    en = _need(name, en, "en", F64, ("n", 2), "copy", cells=(0, 1 << 30))
+    _need(name, skipped, "skipped", I64, 1)
+    zone, south = _zone(name, zone, south)
+    _on_device(name, en, skipped)
+    n = en.shape[0]
+    lonlat = torch.empty((n, 2), dtype=torch.float64, device=en.device)
+    if n:
+        with torch.cuda.device(en.device):
+            L.check(L.lib().bn_utm_geodetic(_p(en), n, zone, south, _p(lonlat), _p(skipped), _stream()), "bn_utm_geodetic")
+    return lonlat
+
+
+def grid_pixels(rpc, dsm, xoff, yoff, res, zone, south, rows=None, colrow=None, counts=None):
+    """The pixel of an image that every cell of a height grid projects to (bn_grid_pixels): rpc a camera.Rpc, dsm (H, W) float32
+    with its Grid's origin and resolution, in the UTM `zone`.  rows = (row0, row1): only those rows are written (the others are
+    uninitialised unless `colrow` comes in) and counted.  -> colrow (H, W, 2) float64 = (col, row), NaN where a cell is counted,
+    counts (1,) int64, accumulated into when given."""
+    name = "grid_pixels"
+    _need(name, dsm, **VIS_DSM)
+    zone, south = _zone(name, zone, south)
+    xoff, yoff, res = float(xoff), float(yoff), float(res)
+    if not (res > 0 and math.isfinite(res) and math.isfinite(xoff) and math.isfinite(yoff)):
+        raise ValueError(f"{name}: origin ({xoff}, {yoff}) must be finite and resolution {res} positive and finite")
+    H, W = dsm.shape
+    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= row0 <= row1 <= H:
+        raise ValueError(f"{name}: rows ({row0}, {row1}) outside [0, {H}]")
+    colrow = _out(name, colrow, "colrow", F64, (H, W, 2), dsm.device, torch.empty)
+    counts = _out(name, counts, "counts", I64, (1,), dsm.device, flat=True)
+    _on_device(name, dsm, colrow, counts)
+    with torch.cuda.device(dsm.device):
+        L.check(L.lib().bn_grid_pixels(rpc.ref(), _p(dsm), H, W, xoff, yoff, res, row0, row1, zone, south, _p(colrow), _p(counts), _stream()),
+                "bn_grid_pixels")
+    return colrow, counts
+
+
+GATHER_MODES = {"bilinear": L.BN_GATHER_BILINEAR, "nearest": L.BN_GATHER_NEAREST}
+
+
+def image_gather(img, Hi, Wi, C_, strides, colrow, vis=None, cells=None, mode="bilinear", out=None, state=None, counts=None):
+    """An image gathered at the pixels of n cells (bn_image_gather).  img: a contiguous float32 device buffer read through the
+    element strides (row, col, channel) - no copy; colrow (..., 2) float64 = (col, row) per cell, vis uint8 per cell or None
+    (only BN_VIS_VISIBLE cells are kept); cells = (n0, n1): only those cells are written (the others are uninitialised unless
+    `out` / `state` come in) and counted.  -> out (C, n) float32, state (n,) uint8 in {0 no data, 1 outside, 2 occluded, 3 kept},
+    counts (4,) int64, accumulated into when given."""
+    name = "image_gather"
+    Hi, Wi, C_ = int(Hi), int(Wi), int(C_)
+    if mode not in GATHER_MODES:
+        raise ValueError(f"{name}: mode {mode!r} ('bilinear' or 'nearest')")
+    if Hi < 1 or Wi < 1 or not 1 <= C_ <= L.BN_GATHER_MAX_CHANNELS:
+        raise ValueError(f"{name}: an image of {Hi} x {Wi} pixels and {C_} channels (at least 1 x 1, 1 to {L.BN_GATHER_MAX_CHANNELS} channels)")
+    _need(name, img, "image", F32)
+    sr, sc, sp = (int(s) for s in strides)
+    last = (Hi - 1) * sr + (Wi - 1) * sc + (C_ - 1) * sp
+    if min(sr, sc, sp) < 0 or last >= img.numel():
+        raise ValueError(f"{name}: image of {img.numel()} elements is read through the strides {(sr, sc, sp)} up to element {last}")
+    _need(name, colrow, "colrow", F64)
+    if colrow.dim() < 1 or colrow.shape[-1] != 2 or colrow.numel() > 1 << 31:
+        raise ValueError(f"{name}: colrow {tuple(colrow.shape)} is not (..., 2) with at most 2^30 cells")
+    n = colrow.numel() // 2
+    _maybe(name, vis, "vis", U8, n)
+    n0, n1 = (0, n) if cells is None else (int(cells[0]), int(cells[1]))
+    if not 0 <= n0 <= n1 <= n:
+        raise ValueError(f"{name}: cells ({n0}, {n1}) outside [0, {n}]")
+    out = _out(name, out, "out", F32, (C_, n), colrow.device, torch.empty, flat=True)
+    state = _out(name, state, "state", U8, (n,), colrow.device, torch.empty, flat=True)
+    counts = _out(name, counts, "counts", I64, (4,), colrow.device, flat=True)
+    _on_device(name, img, colrow, vis, out, state, counts)
+    with torch.cuda.device(colrow.device):
+        L.check(L.lib().bn_image_gather(_p(img), Hi, Wi, C_, sr, sc, sp, _p(colrow), _p(vis), n0, n1, GATHER_MODES[mode], _p(out), n,
+                                        _p(state), _p(counts), _stream()), "bn_image_gather")
+    return out, state, counts

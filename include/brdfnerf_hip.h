@@ -990,6 +990,77 @@ int bn_grid_visibility(const float *dsm, int32_t H, int32_t W, double res, int32
 int bn_points_visibility(const double *enz, int64_t R, const float *dsm, int32_t H, int32_t W, double xoff, double yoff, double res,
                          const double *dirs, int32_t K, double eps, double zmax, uint8_t *vis, int32_t *hit, long long *counts,
                          void *stream);
+/* Orthophoto of an observed image (additive to ABI 7): every cell of a surface model is taken to the pixel of a satellite image
+ * that saw it, and the image - or any per-pixel raster in image geometry - is gathered there.  The ortho entries above splat a
+ * VIEW's rays into cells; this is the opposite direction.  There is NO upstream counterpart - the reference never orthorectifies
+ * an image and reaches UTM only forwards, through pyproj - so the rule is this project's own.  Everything up to the gather's cast
+ * is float64 and every operation is rounded on its own (csrc/orthophoto.hip is compiled with fp contraction off).
+ *
+ * 1. cell         cell (j, i) of the north-up grid (row 0 is the northern edge, as in the visibility entries):
+ *                 e = xoff + ((double)i + 0.5) res ; nn = yoff - ((double)j + 0.5) res ; a = (double)dsm[j][i]
+ * 2. inverse UTM  (e, nn) in `zone` (south = 1: the false northing of 10,000,000 m is taken off) -> (lon, lat) in degrees:
+ *                 Karney 2011, eq. 36 and eqs. 19-21, with n, e and k0 A as step 4 of "The rays of a satellite view" forms them.
+ *                 The coefficients, on the host, in Horner form in n with every fraction one division:
+ *                   beta1 = n/2 - 2n^2/3 + 37n^3/96 - n^4/360 - 81n^5/512 + 96199n^6/604800
+ *                   beta2 = n^2/48 + n^3/15 - 437n^4/1440 + 46n^5/105 - 1118711n^6/3870720
+ *                   beta3 = 17n^3/480 - 37n^4/840 - 209n^5/4480 + 5569n^6/90720
+ *                   beta4 = 4397n^4/161280 - 11n^5/504 - 830251n^6/7257600
+ *                   beta5 = 4583n^5/161280 - 108847n^6/3991680          beta6 = 20648693n^6/638668800
+ *                 xi = (nn - false_north) / k0A ; eta = (e - 500000) / k0A
+ *                 xi' = xi - sum_j beta_j sin(2 j xi) cosh(2 j eta) ; eta' = eta - sum_j beta_j cos(2 j xi) sinh(2 j eta), j ascending,
+ *                   the six complex sines sin(2 j (xi + i eta)) by the angle-addition recurrence of the forward series from ONE
+ *                   sin, cos, sinh and cosh of the double angle
+ *                 lon = lon0 + atan2(sinh eta', cos xi') 180 / pi          (lon0 = 6 zone - 183; times 180, then divided by pi)
+ *                 tau' = sin xi' / sqrt(sinh eta' sinh eta' + cos xi' cos xi')
+ *                 tau = tau', then BN_UTM_NEWTON_ITERS times, without a data-dependent exit, with e2m = 1 - e e:
+ *                   r = sqrt(1 + tau tau) ; sigma = sinh(e atanh(e tau / r)) ; t = tau sqrt(1 + sigma sigma) - sigma r
+ *                   tau = tau + (tau' - t) / sqrt(1 + t t) * (1 + e2m (tau tau)) / (e2m r)
+ *                 lat = atan(tau) 180 / pi
+ *                 A point whose lon or lat is not finite gives (NaN, NaN) and is counted.  The device's float64 sin, cos, sinh,
+ *                 cosh, atan2, atanh and atan are not bit-specified: this step is held to a numpy statement within 1e-6 m carried
+ *                 to degrees, and the statement to the project's own FORWARD series by the round trip (7.5e-9 m measured).  Not
+ *                 checked against pyproj.
+ * 3. pixel        steps 1 and 2 of "The rays of a satellite view" on (lon, lat, a) -> (col, row).
+ *                 A cell whose a, lon, lat, col or row is NaN or not finite has NaN in both outputs and is counted once.
+ * 4. gather       A pixel index is its coordinate: (col, row) = (k, l) is the centre of pixel (l, k).  Per cell, in this order:
+ *                   col or row is NaN                                              state BN_GATHER_NODATA
+ *                   !(0 <= col && col <= Wi - 1 && 0 <= row && row <= Hi - 1)      state BN_GATHER_OUTSIDE
+ *                   vis != NULL && vis[cell] != BN_VIS_VISIBLE                     state BN_GATHER_OCCLUDED
+ *                   otherwise                                                      state BN_GATHER_KEPT
+ *                 In the first three states every channel is NaN.  Pixel (r, c) of channel ch is img[r s_row + c s_col + ch
+ *                 s_chan] (element strides: s_chan = 1, s_col = C, s_row = Wi C for an [Hi Wi][C] buffer; s_chan = Hi Wi, s_row =
+ *                 Wi, s_col = 1 for [C][Hi][Wi] planes).
+ *                 BN_GATHER_BILINEAR: c0 = max(min((int)floor(col), Wi - 2), 0), c1 = min(c0 + 1, Wi - 1), fx = col - (double)c0
+ *                 (at col = Wi - 1 the taps are the last two and fx = 1; with Wi == 1, c0 = c1 = 0 and fx = 0); rows likewise;
+ *                 v = (1 - fy) ((1 - fx) p00 + fx p01) + fy ((1 - fx) p10 + fx p11) with the four taps widened to float64, p_rc the
+ *                 tap of row r_r and column c_c; out = (float)v.  Plain arithmetic: a NaN tap propagates even at weight 0.
+ *                 BN_GATHER_NEAREST: c = min((int)floor(col + 0.5), Wi - 1), rows likewise; the pixel's 32 bits are copied.
+ *
+ * bn_utm_geodetic  en float64 [n][2] = (east, north) -> lonlat float64 [n][2]; skipped[0] += the counted points  (step 2)
+ * bn_grid_pixels   rpc is a HOST pointer; dsm float32 [H][W]; the cells of rows [row0, row1) -> colrow float64 [H][W][2] = (col,
+ *                  row), only the band's rows written; counts[0] += the counted cells.  An empty band launches nothing.  Equal bit
+ *                  for bit to bn_utm_geodetic followed by bn_rpc_project on the same cell centres.  (steps 1-3)
+ * bn_image_gather  cells [n0, n1) of colrow float64 [.][2], vis uint8 [.] (nullable), state uint8 [.] and out float32, channel ch of
+ *                  cell c at out[ch out_chan_stride + c]: every per-cell array is indexed by the cell itself, so a band of
+ *                  cells writes its part of whole buffers.  counts uint64 [4] += the cells of the call in each state.  (step 4)
+ * skipped and counts are device memory, the CALLER zeroes them, one integer atomic per counter and block; there is no float atomic.
+ * Every bit depends on the inputs alone - not on blocks, row bands, cell ranges or the number of ranks.
+ * Refused (BN_EINVAL, nothing launched, buffers untouched): NULL en, lonlat, skipped, rpc, dsm, colrow, counts, img, out or state;
+ * n < 0 or over 2^30; a zone outside [1, 60]; south other than 0 or 1; H or W < 1, or H W > 2^30; rows outside [0, H] or row0 >
+ * row1; res not positive and finite; a non-finite grid origin; a scale of zero or a non-finite entry in the descriptor; C outside
+ * [1, BN_GATHER_MAX_CHANNELS]; Hi or Wi < 1; a negative stride; n0 < 0, n0 > n1 or n1 over 2^30; another mode.  The image buffer's
+ * extent is the caller's to check: the taps lie in [0, Hi - 1] x [0, Wi - 1] and nowhere else. */
+#define BN_UTM_NEWTON_ITERS 4
+#define BN_GATHER_MAX_CHANNELS 32
+enum { BN_GATHER_BILINEAR = 0, BN_GATHER_NEAREST = 1 };
+enum { BN_GATHER_NODATA = 0, BN_GATHER_OUTSIDE = 1, BN_GATHER_OCCLUDED = 2, BN_GATHER_KEPT = 3 };
+int bn_utm_geodetic(const double *en, int64_t n, int32_t zone, int32_t south, double *lonlat, unsigned long long *skipped,
+                    void *stream);
+int bn_grid_pixels(const bn_rpc *rpc, const float *dsm, int32_t H, int32_t W, double xoff, double yoff, double res, int32_t row0,
+                   int32_t row1, int32_t zone, int32_t south, double *colrow, unsigned long long *counts, void *stream);
+int bn_image_gather(const float *img, int32_t Hi, int32_t Wi, int32_t C, int64_t s_row, int64_t s_col, int64_t s_chan,
+                    const double *colrow, const uint8_t *vis, int64_t n0, int64_t n1, int32_t mode, float *out,
+                    int64_t out_chan_stride, uint8_t *state, unsigned long long *counts, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
