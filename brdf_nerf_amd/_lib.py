@@ -73,12 +73,18 @@ BN_VIS_BLOCKED, BN_VIS_VISIBLE, BN_VIS_NODATA, BN_VIS_MAX_DIRS = 0, 1, 2, 4096
 BN_UTM_NEWTON_ITERS, BN_GATHER_MAX_CHANNELS = 4, 32
 BN_GATHER_BILINEAR, BN_GATHER_NEAREST = 0, 1
 BN_GATHER_NODATA, BN_GATHER_OUTSIDE, BN_GATHER_OCCLUDED, BN_GATHER_KEPT = 0, 1, 2, 3
+BN_MOSAIC_MAX_VIEWS, BN_MOSAIC_MAX_CHANNELS, BN_MOSAIC_USED, BN_MOSAIC_NONFINITE = 32, 4, 3, 4
 
 
 class Rpc(C.Structure):               # bn_rpc: 90 doubles
     _fields_ = [(k, C.c_double) for k in ("row_offset", "col_offset", "lat_offset", "lon_offset", "alt_offset", "row_scale",
                                           "col_scale", "lat_scale", "lon_scale", "alt_scale")] + \
                [(k, C.c_double * 20) for k in ("row_num", "row_den", "col_num", "col_den")]
+
+
+class MosaicView(C.Structure):        # bn_mosaic_view: one image of bn_grid_mosaic, 776 bytes
+    _fields_ = [("img", fptr), ("vis", fptr), ("Hi", C.c_int32), ("Wi", C.c_int32), ("s_row", C.c_int64), ("s_col", C.c_int64),
+                ("s_chan", C.c_int64), ("rank", C.c_int32), ("rpc", Rpc)]
 
 
 class NormalReg(C.Structure):         # bn_normal_reg
@@ -199,6 +205,9 @@ _SIGS = {
                                  C.c_int32, C.c_int32, fptr, fptr, fptr]),
     "bn_image_gather": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, fptr, fptr, C.c_int64,
                                   C.c_int64, C.c_int32, fptr, C.c_int64, fptr, fptr, fptr]),
+    "bn_grid_mosaic": (C.c_int, [C.POINTER(MosaicView), fptr, C.c_int32, C.c_int32, fptr, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                 C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr,
+                                 fptr, fptr]),
     "bn_ssim_map": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, fptr, C.c_double,
                               C.c_double, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, fptr, fptr, fptr]),
     "bn_grid_normals": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_double, fptr, fptr]),

@@ -11,6 +11,7 @@
 //                         + x / occur, so the fused launch gives the two-launch chain's bits
 //   image_gather_kernel   one lane per cell of [n0, n1): the state of the cell (no data, outside, occluded, kept), then the
 //                         bilinear taps in float64 or the nearest pixel's 32 bits, channel after channel through element strides
+//                         (gather_rule.h: the state, the taps and the expression, shared with mosaic.hip)
 //
 // The descriptor's 80 coefficients travel in the kernel arguments (as in rpc_project_kernel): a wave reads them through the scalar
 // cache once.  Counted cells and the four states are summed per block and added with ONE integer atomic per counter
@@ -20,6 +21,7 @@
 #include "common.h"
 #include "brdfnerf_hip.h"
 #include "block_sums.h"
+#include "gather_rule.h"
 #include "geodesy.h"
 #include "rpc_poly.h"
 // every float64 operation below is rounded on its own (see above); the build also passes -ffp-contract=off for this file
@@ -84,52 +86,25 @@ struct GatherArgs {
   unsigned long long *counts;
 };
 
-// the two taps of one axis (bilinear): x in [0, n - 1] -> t0, t1 in [0, n - 1] and the weight of t1
-__device__ __forceinline__ void taps(double x, int32_t n, int32_t &t0, int32_t &t1, double &f) {
-  const int32_t fl = (int32_t)floor(x);
-  t0 = fl < n - 2 ? fl : n - 2;
-  t0 = t0 > 0 ? t0 : 0;                         // n == 1: both taps are pixel 0
-  t1 = t0 + 1 < n ? t0 + 1 : n - 1;
-  f = x - (double)t0;
-}
-
-__device__ __forceinline__ int32_t nearest_tap(double x, int32_t n) {
-  const int32_t r = (int32_t)floor(x + 0.5);
-  return r < n - 1 ? r : n - 1;
-}
-
 __global__ __launch_bounds__(OPH_BLOCK)
 void image_gather_kernel(const GatherArgs A) {
   const int64_t c = A.n0 + (int64_t)blockIdx.x * OPH_BLOCK + threadIdx.x;
   int st = -1;                                   // a lane outside the range counts nowhere
   if (c < A.n1) {
     const double col = A.colrow[2 * c], row = A.colrow[2 * c + 1];
-    if (isnan(col) || isnan(row)) st = BN_GATHER_NODATA;
-    else if (!(col >= 0.0 && col <= (double)(A.Wi - 1) && row >= 0.0 && row <= (double)(A.Hi - 1))) st = BN_GATHER_OUTSIDE;
-    else if (A.vis && A.vis[c] != BN_VIS_VISIBLE) st = BN_GATHER_OCCLUDED;
-    else st = BN_GATHER_KEPT;
+    st = gather_rule::cell_state(col, row, A.Hi, A.Wi, A.vis, c);
     A.state[c] = (uint8_t)st;
     float *out = A.out + c;
     if (st != BN_GATHER_KEPT) {
       for (int ch = 0; ch < A.C; ++ch) out[ch * A.out_chan_stride] = __builtin_nanf("");
     } else if (A.mode == BN_GATHER_NEAREST) {
-      const int64_t at = (int64_t)nearest_tap(row, A.Hi) * A.s_row + (int64_t)nearest_tap(col, A.Wi) * A.s_col;
+      const int64_t at = gather_rule::nearest_at(col, row, A.Hi, A.Wi, A.s_row, A.s_col);
       const uint32_t *src = reinterpret_cast<const uint32_t *>(A.img);
       uint32_t *dst = reinterpret_cast<uint32_t *>(out);
       for (int ch = 0; ch < A.C; ++ch) dst[ch * A.out_chan_stride] = src[at + ch * A.s_chan];      // the pixel's 32 bits
     } else {
-      int32_t c0, c1, r0, r1;
-      double fx, fy;
-      taps(col, A.Wi, c0, c1, fx);
-      taps(row, A.Hi, r0, r1, fy);
-      const int64_t a00 = r0 * A.s_row + c0 * A.s_col, a01 = r0 * A.s_row + c1 * A.s_col;
-      const int64_t a10 = r1 * A.s_row + c0 * A.s_col, a11 = r1 * A.s_row + c1 * A.s_col;
-      for (int ch = 0; ch < A.C; ++ch) {
-        const float *p = A.img + ch * A.s_chan;
-        const double p00 = (double)p[a00], p01 = (double)p[a01], p10 = (double)p[a10], p11 = (double)p[a11];
-        const double v = (1.0 - fy) * ((1.0 - fx) * p00 + fx * p01) + fy * ((1.0 - fx) * p10 + fx * p11);
-        out[ch * A.out_chan_stride] = (float)v;
-      }
+      const gather_rule::Taps4 t = gather_rule::bilinear_taps(col, row, A.Hi, A.Wi, A.s_row, A.s_col);
+      for (int ch = 0; ch < A.C; ++ch) out[ch * A.out_chan_stride] = gather_rule::bilinear(A.img + ch * A.s_chan, t);
     }
   }
   for (int s = 0; s < 4; ++s) block_sums::block_count(st == s, A.counts + s);

@@ -1564,3 +1564,75 @@ def image_gather(img, Hi, Wi, C_, strides, colrow, vis=None, cells=None, mode="b
         L.check(L.lib().bn_image_gather(_p(img), Hi, Wi, C_, sr, sc, sp, _p(colrow), _p(vis), n0, n1, GATHER_MODES[mode], _p(out), n,
                                         _p(state), _p(counts), _stream()), "bn_image_gather")
     return out, state, counts
+
+
+MOSAIC_MAPS = ("best", "best_val", "mean", "std")
+
+
+def grid_mosaic(views, C_, dsm, xoff, yoff, res, zone, south, rows=None, mode="bilinear", colrow=None, count=None, best=None,
+                best_val=None, mean=None, std=None, counts=None, sums=None, want=MOSAIC_MAPS):
+    """The cells of a height grid under K images in one launch (bn_grid_mosaic).  views: K tuples (img, Hi, Wi, strides, vis, rank,
+    rpc) - img a contiguous float32 device buffer of C_ channels read through the element strides (row, col, channel), as
+    image_gather reads it; vis (H, W) uint8 of grid_visibility towards that view, or None; rank an integer, the smaller wins
+    `best`; rpc a camera.Rpc.  dsm (H, W) float32 with its Grid's origin and resolution, in the UTM `zone`; colrow (K, H, W, 2)
+    float64 or None: the views' pixels as grid_pixels gives them, used in place of the projection.  rows = (row0, row1): only
+    those rows are written (the others are uninitialised unless the outputs come in) and counted.  count (H, W) uint8, best (H, W)
+    int32, best_val / mean / std (C_, H, W) float32, counts (K, 5) int64 and sums (3,) int64 = (cells, q, skipped) may be given -
+    counts and sums are accumulated into; a map that is neither given nor named in `want` is not computed (None).
+    -> {"count", "best", "best_val", "mean", "std", "counts", "sums"}."""
+    name = "grid_mosaic"
+    views = list(views)
+    K, C_ = len(views), int(C_)
+    if not 1 <= K <= L.BN_MOSAIC_MAX_VIEWS:
+        raise ValueError(f"{name}: {K} views (1 to {L.BN_MOSAIC_MAX_VIEWS})")
+    if not 1 <= C_ <= L.BN_MOSAIC_MAX_CHANNELS:
+        raise ValueError(f"{name}: {C_} channels (1 to {L.BN_MOSAIC_MAX_CHANNELS})")
+    if mode not in GATHER_MODES:
+        raise ValueError(f"{name}: mode {mode!r} ('bilinear' or 'nearest')")
+    _need(name, dsm, **VIS_DSM)
+    zone, south = _zone(name, zone, south)
+    xoff, yoff, res = float(xoff), float(yoff), float(res)
+    if not (res > 0 and math.isfinite(res) and math.isfinite(xoff) and math.isfinite(yoff)):
+        raise ValueError(f"{name}: origin ({xoff}, {yoff}) must be finite and resolution {res} positive and finite")
+    H, W = dsm.shape
+    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= row0 <= row1 <= H:
+        raise ValueError(f"{name}: rows ({row0}, {row1}) outside [0, {H}]")
+    held, specs = [], []
+    for k, (img, Hi, Wi, strides, vis, rank, rpc) in enumerate(views):
+        Hi, Wi = int(Hi), int(Wi)
+        _need(name, img, f"image {k}", F32)
+        sr, sc, sp = (int(s) for s in strides)
+        last = (Hi - 1) * sr + (Wi - 1) * sc + (C_ - 1) * sp
+        if Hi < 1 or Wi < 1 or min(sr, sc, sp) < 0 or last >= img.numel():
+            raise ValueError(f"{name}: image {k} of {img.numel()} elements is read as {Hi} x {Wi} pixels through the strides "
+                             f"{(sr, sc, sp)} up to element {last}")
+        _maybe(name, vis, f"vis {k}", U8, (H, W))
+        if isinstance(rank, bool) or int(rank) != rank or not -(1 << 31) <= int(rank) < 1 << 31:
+            raise ValueError(f"{name}: rank {rank!r} of view {k} is not a 32-bit integer")
+        held += [img, vis]
+        specs.append((img, vis, Hi, Wi, sr, sc, sp, int(rank), rpc.struct))
+    _maybe(name, colrow, "colrow", F64, (K, H, W, 2))
+    dev = dsm.device
+    wanted = lambda t, key: t is not None or key in want
+    count = _out(name, count, "count", U8, (H, W), dev, torch.empty)
+    best = _out(name, best, "best", I32, (H, W), dev, torch.empty) if wanted(best, "best") else None
+    best_val = _out(name, best_val, "best_val", F32, (C_, H, W), dev, torch.empty) if wanted(best_val, "best_val") else None
+    mean = _out(name, mean, "mean", F32, (C_, H, W), dev, torch.empty) if wanted(mean, "mean") else None
+    std = _out(name, std, "std", F32, (C_, H, W), dev, torch.empty) if wanted(std, "std") else None
+    counts = _out(name, counts, "counts", I64, (K, 5), dev)
+    sums = _out(name, sums, "sums", I64, (3,), dev, flat=True)
+    _on_device(name, dsm, colrow, count, best, best_val, mean, std, counts, sums, *held)
+    table = (L.MosaicView * K)()
+    for v, (img, vis, *scalars, rpc) in zip(table, specs):
+        v.img, v.vis = img.data_ptr(), None if vis is None else vis.data_ptr()
+        v.Hi, v.Wi, v.s_row, v.s_col, v.s_chan, v.rank = scalars
+        v.rpc = rpc
+    with torch.cuda.device(dev):
+        # the same bytes on the device, which the kernel reads; the library checks the host copy and copies nothing.  The copy and
+        # the launch are on one stream, so the buffer may go back to the allocator when this call returns
+        table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=U8).to(dev)
+        L.check(L.lib().bn_grid_mosaic(table, _p(table_dev), K, C_, _p(dsm), H, W, xoff, yoff, res, row0, row1, zone, south,
+                                       GATHER_MODES[mode], _p(colrow), _p(count), _p(best), _p(best_val), _p(mean), _p(std),
+                                       _p(counts), _p(sums), _stream()), "bn_grid_mosaic")
+    return {"count": count, "best": best, "best_val": best_val, "mean": mean, "std": std, "counts": counts, "sums": sums}

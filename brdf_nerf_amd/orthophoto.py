@@ -31,8 +31,8 @@ Refused by name (ValueError, before any launch): host tensors, a DSM that is not
 that is not float32 and contiguous or does not hold H_img W_img pixels of 1 to 32 channels, points that are not float64 (n, 3), a
 zone outside 1-60, a view_dir that is not finite or does not point upwards, an unknown mode or layout, rows outside [0, H].
 
-Not covered: fusing several views into one mosaic, radiometric normalisation, per-cell view directions, GeoTIFF I/O, pyproj parity
-of the inverse UTM (it is held to the project's own forward series).
+Not covered: radiometric normalisation, per-cell view directions, GeoTIFF I/O, pyproj parity of the inverse UTM (it is held to the
+project's own forward series).  Several views fused into one mosaic: mosaic.py.
 """
 import math
 

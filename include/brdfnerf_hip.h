@@ -1061,6 +1061,69 @@ int bn_grid_pixels(const bn_rpc *rpc, const float *dsm, int32_t H, int32_t W, do
 int bn_image_gather(const float *img, int32_t Hi, int32_t Wi, int32_t C, int64_t s_row, int64_t s_col, int64_t s_chan,
                     const double *colrow, const uint8_t *vis, int64_t n0, int64_t n1, int32_t mode, float *out,
                     int64_t out_chan_stride, uint8_t *state, unsigned long long *counts, void *stream);
+/* Orthomosaic of several observed images (additive to ABI 7): the cells of a surface model under K images at once.  A site has 10
+ * to 30 views and each sees another side of every building; one launch takes a cell to its geodetic point ONCE, walks the views
+ * and keeps only the results - how many views saw the cell, the best of them, the mean and the spread of what they saw (the
+ * multi-view photo-consistency of the surface model: a wrong altitude sends a cell to different ground in every image).  There is
+ * NO upstream counterpart.  Float64, every operation rounded on its own (csrc/mosaic.hip is compiled with fp contraction off).
+ *
+ * views_host / views_dev: the same K records in host memory - read and checked before the launch - and in device memory, which
+ *   the kernel reads (the CALLER makes the copy; 90 doubles per view do not fit into kernel arguments).  K in [1,
+ *   BN_MOSAIC_MAX_VIEWS].  img, Hi, Wi, s_row, s_col, s_chan: as bn_image_gather takes them, C channels in every view, C in [1,
+ *   BN_MOSAIC_MAX_CHANNELS]; vis: uint8 [H][W] of bn_grid_visibility towards that view's sensor, or NULL (never occluded); rank:
+ *   the smaller rank wins `best`, ties go to the lower view index; rpc: the view's descriptor.
+ * dsm, H, W, xoff, yoff, res, row0, row1, zone, south: as bn_grid_pixels takes them.  mode: BN_GATHER_BILINEAR or BN_GATHER_NEAREST.
+ * colrow_in (nullable): float64 [K][H][W][2] = (col, row) per view and cell, on the device.  When given, steps 2 and 3a are skipped
+ *   and these pixels are used (what bn_grid_pixels wrote for every view).
+ *
+ * Per cell (j, i) of rows [row0, row1):
+ * 1. centre     e, nn, a as step 1 of "Orthophoto of an observed image".
+ * 2. point      bad0 = (step 2 of that section refuses (e, nn)) ; (lon, lat) from it - once per cell, not per view.
+ * 3. views      n = 0 ; m_c = 0.0, M2_c = 0.0 for c < C ; then for k = 0 .. K - 1, ascending:
+ *    a. pixel   (col, row) = step 3 of that section under rpc_k on (lon, lat, a); both NaN if bad0 || !(isfinite(a) && isfinite(col)
+ *               && isfinite(row)).  These are bn_grid_pixels' bits for view k: the same device functions on the same operands.
+ *    b. state   step 4's state with Hi_k, Wi_k, vis_k: BN_GATHER_NODATA 0, BN_GATHER_OUTSIDE 1, BN_GATHER_OCCLUDED 2, else kept.
+ *    c. value   if kept: v_c (float32) for c < C in `mode`, step 4's taps and expression: bn_image_gather's bits.
+ *    d. if any v_c is NaN or infinite the view's state is BN_MOSAIC_NONFINITE 4 and it contributes nothing.
+ *    e. otherwise the state is BN_MOSAIC_USED 3 and
+ *               n = n + 1
+ *               per channel: x = (double)v_c ; delta = x - m_c ; m_c = m_c + delta / (double)n ; M2_c = M2_c + delta * (x - m_c)
+ *               (Welford's update: with float32 values near 4096 that spread by 1e-3 the sum-of-squares form q / n - m m loses
+ *               the spread's third digit)
+ *               if n == 1 || rank_k < best_rank: view k is the best, best_rank = rank_k, its v_c (32 bits each) are kept.
+ * Outputs, each a plain store of the lane's own cell, only the band's rows written; best, best_val, mean, std and sums are
+ * nullable one by one, count and counts are required:
+ *   count     uint8 [H][W]      n
+ *   best      int32 [H][W]      the best view's index, -1 when n == 0
+ *   best_val  float32 [C][H][W] the best view's values, bits copied; NaN when n == 0
+ *   mean      float32 [C][H][W] (float)m_c ; NaN when n == 0
+ *   std       float32 [C][H][W] (float)sqrt(M2_c / (double)n): the population's, 0 at n == 1 ; NaN when n == 0
+ *   counts    uint64 [K][5]     += the cells of the band per view and state 0 to 4
+ *   sums      uint64 [3]        += (cells, q, skipped) over the cells with n >= 2: cells += 1 per cell; per channel, s = sqrt(M2_c /
+ *                               (double)n): q += llrint(s 2^20) if s < 2^20, otherwise skipped += 1.  The photo-consistency of
+ *                               the grid is q / (cells C 2^20).
+ * counts and sums are device memory, the CALLER zeroes them, one integer atomic per counter and block; there is no float atomic.
+ * Every bit depends on the inputs alone - not on blocks, row bands or the number of ranks (the bands are gathered, counts and sums
+ * add up).  An empty band is accepted and launches nothing.
+ * Refused (BN_EINVAL, nothing launched, buffers untouched): NULL views_host, views_dev, dsm, count or counts; K or C out of range;
+ * everything bn_grid_pixels refuses of the grid, the rows and the zone; per view a NULL img, Hi or Wi < 1, a negative stride, a
+ * scale of zero or a non-finite entry in the descriptor (with colrow_in too); another mode.  The image buffers' extents are the
+ * caller's to check, as in bn_image_gather. */
+#define BN_MOSAIC_MAX_VIEWS 32
+#define BN_MOSAIC_MAX_CHANNELS 4
+enum { BN_MOSAIC_USED = 3, BN_MOSAIC_NONFINITE = 4 };
+typedef struct {
+  const float *img;          /* device, read through the strides, as bn_image_gather */
+  const uint8_t *vis;        /* device [H][W] of grid_visibility for this view, or NULL: never occluded */
+  int32_t Hi, Wi;
+  int64_t s_row, s_col, s_chan;
+  int32_t rank;              /* smaller wins `best`; ties go to the lower view index */
+  bn_rpc rpc;
+} bn_mosaic_view;
+int bn_grid_mosaic(const bn_mosaic_view *views_host, const bn_mosaic_view *views_dev, int32_t K, int32_t C, const float *dsm,
+                   int32_t H, int32_t W, double xoff, double yoff, double res, int32_t row0, int32_t row1, int32_t zone,
+                   int32_t south, int32_t mode, const double *colrow_in, uint8_t *count, int32_t *best, float *best_val, float *mean,
+                   float *std, unsigned long long *counts, unsigned long long *sums, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
