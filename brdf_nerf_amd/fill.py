@@ -16,7 +16,7 @@ is unique this IS upstream's answer; on a tie upstream returns the value of some
 tree's traversal order, and the rule picks the first in row-major order.
 
 Everything is integer, so the result does not depend on how the rows are split (rows=) or on how many GPUs shared the grid:
-each rank fills a band of rows, the bands are gathered, and (holes, max d2) merge by one SUM and one MAX all-reduce.
+each rank fills a band of rows, the bands are gathered, and (holes, max d2) merge by one SUM and one MAX all-reduce (gridwalk.py).
 
 Refused by name: host tensors, a dtype other than float32, a grid that is not 2-D and contiguous, more than 8192 cells a side,
 rows outside [0, H], a grid without a known cell (upstream's griddata raises there too).
@@ -28,6 +28,7 @@ import math
 import torch
 
 from . import functions as Fn
+from .gridwalk import GridWalk
 
 
 @torch.no_grad()
@@ -39,28 +40,22 @@ def fill_holes(dsm, rows=None, group=None, want_source=False):
     with `rows`, the rows outside the band are returned as they came (holes included) and `source` is -1 there.
     -> {"filled" (H, W) float32, "holes" int, "max_dist" float = sqrt(largest d2)} (+ "source" (H, W) int32 flat indices)."""
     import torch.distributed as dist
-    from .distributed import allreduce_, gather_rows, row_band, world_info
     Fn._need("fill_holes", dsm, "dsm", torch.float32, **Fn.FILL_GRID)
     H, W = dsm.shape
-    _, world = world_info(group)
-    rows = row_band("fill_holes", H, rows, group)
+    walk = GridWalk("fill_holes", H, rows, group)
     near_row = Fn.grid_nearest_col(dsm)                    # refuses a host tensor before any launch
     if int(near_row.max()) < 0:
         raise ValueError(f"fill_holes: the {H} x {W} grid has no known cell (every cell is NaN)")
-    dst, source, _, counts = Fn.grid_fill(dsm, near_row, rows=rows, want_source=want_source)
-    if world > 1:
-        dst = gather_rows(dst[rows[0]:rows[1]], group)
+    dst, source, _, counts = Fn.grid_fill(dsm, near_row, rows=walk.rows, want_source=want_source)
+    if walk.world > 1:
+        dst = walk.join(dst)
         if want_source:
-            source = gather_rows(source[rows[0]:rows[1]], group)
-        if dst.shape[0] != H:
-            raise ValueError(f"fill_holes: the ranks' bands cover {dst.shape[0]} rows of {H}")
+            source = walk.join(source)
         holes, far = counts[0:1].clone(), counts[1:2].clone()
-        allreduce_(holes, dist.ReduceOp.SUM, group)
-        allreduce_(far, dist.ReduceOp.MAX, group)
-        counts = torch.cat([holes, far])
-    elif rows != (0, H):
+        counts = torch.cat([walk.merge(holes), walk.merge(far, dist.ReduceOp.MAX)])
+    elif walk.alone:                                       # the rows outside a lone band: as they came, which no constant states
         band = torch.zeros((H, 1), dtype=torch.bool, device=dsm.device)
-        band[rows[0]:rows[1]] = True
+        band[walk.rows[0]:walk.rows[1]] = True
         dst = torch.where(band, dst, dsm)
         if want_source:
             source = torch.where(band, source, torch.full_like(source, -1))

@@ -774,6 +774,14 @@ def _on_device(name, *tensors):
         raise ValueError(f"{name}: every tensor must be on the device (there is no host path)")
 
 
+def _rows(name, H, rows):
+    """rows = (row0, row1), or None for all H rows, of a grid entry -> (row0, row1), or ValueError by name outside [0, H]."""
+    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= row0 <= row1 <= H:
+        raise ValueError(f"{name}: rows ({row0}, {row1}) outside [0, {H}]")
+    return row0, row1
+
+
 F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
 FILL_GRID = dict(shape=("H", "W"), side=(1, L.BN_FILL_MAX_SIDE))                          # a grid of the hole filling
 VIS_DSM = dict(what="dsm", dtype=F32, shape=("H", "W"), cells=(1, 1 << 30))               # the height grid of the visibility entries
@@ -1075,9 +1083,7 @@ def grid_fill(src, near_row, rows=None, want_source=False, want_dist2=False):
     if near_row.shape != src.shape:
         raise ValueError(f"grid_fill: near_row {tuple(near_row.shape)} is not on the grid {tuple(src.shape)}")
     H, W = src.shape
-    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= row0 <= row1 <= H:
-        raise ValueError(f"grid_fill: rows ({row0}, {row1}) outside [0, {H}]")
+    row0, row1 = _rows("grid_fill", H, rows)
     _on_device("grid_fill", src, near_row)
     dst = torch.empty((H, W), dtype=torch.float32, device=src.device)
     source = torch.empty((H, W), dtype=torch.int32, device=src.device) if want_source else None
@@ -1126,9 +1132,7 @@ def grid_visibility(dsm, res, dirs, eps=0.0, zmax=float("inf"), rows=None, vis=N
     res, eps, zmax = _vis_scalars(name, res, eps, zmax)
     H, W = dsm.shape
     K = dirs.shape[0]
-    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= row0 <= row1 <= H:
-        raise ValueError(f"{name}: rows ({row0}, {row1}) outside [0, {H}]")
+    row0, row1 = _rows(name, H, rows)
     vis = _out(name, vis, "vis", U8, (K, H, W), dsm.device, torch.empty)
     if hit is not None or want_hit:
         hit = _out(name, hit, "hit", I32, (K, H, W), dsm.device, torch.empty)
@@ -1516,9 +1520,7 @@ def grid_pixels(rpc, dsm, xoff, yoff, res, zone, south, rows=None, colrow=None, 
     if not (res > 0 and math.isfinite(res) and math.isfinite(xoff) and math.isfinite(yoff)):
         raise ValueError(f"{name}: origin ({xoff}, {yoff}) must be finite and resolution {res} positive and finite")
     H, W = dsm.shape
-    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= row0 <= row1 <= H:
-        raise ValueError(f"{name}: rows ({row0}, {row1}) outside [0, {H}]")
+    row0, row1 = _rows(name, H, rows)
     colrow = _out(name, colrow, "colrow", F64, (H, W, 2), dsm.device, torch.empty)
     counts = _out(name, counts, "counts", I64, (1,), dsm.device, flat=True)
     _on_device(name, dsm, colrow, counts)
@@ -1595,9 +1597,7 @@ def grid_mosaic(views, C_, dsm, xoff, yoff, res, zone, south, rows=None, mode="b
     if not (res > 0 and math.isfinite(res) and math.isfinite(xoff) and math.isfinite(yoff)):
         raise ValueError(f"{name}: origin ({xoff}, {yoff}) must be finite and resolution {res} positive and finite")
     H, W = dsm.shape
-    row0, row1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= row0 <= row1 <= H:
-        raise ValueError(f"{name}: rows ({row0}, {row1}) outside [0, {H}]")
+    row0, row1 = _rows(name, H, rows)
     held, specs = [], []
     for k, (img, Hi, Wi, strides, vis, rank, rpc) in enumerate(views):
         Hi, Wi = int(Hi), int(Wi)

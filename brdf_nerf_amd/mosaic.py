@@ -18,7 +18,8 @@ values (bn_image_gather's bits).  A view with a NaN or infinite value is NONFINI
 USED (3) and enter Welford's update of the mean and the sum of squares in float64.  `best` is the used view of the smallest rank,
 ties to the lower index; by default the ranks order the views by elevation, most nadir first.  std is the population's: 0 where
 one view saw the cell.  The consistency of the grid is the mean of std over the cells seen by at least two views and the channels,
-summed in integers of 2^-20.  Everything depends on the inputs alone: not on row bands (rows=) or on how many GPUs shared the grid.
+summed in integers of 2^-20.  Everything depends on the inputs alone: not on row bands (rows=) or on how many GPUs shared the grid
+(gridwalk.py: the bands are gathered, every counter merges by one SUM all-reduce).
 
 Refused by name (ValueError, before any launch): an empty list of views or more than 32, views of different channel counts or more
 than 4 channels, a rank that is not K integers, view_dirs that are not (K, 3), finite and pointing upwards, a colrow that is not
@@ -26,30 +27,20 @@ than 4 channels, a rank that is not K integers, view_dirs that are not (K, 3), f
 
 Not covered: a median, radiometric normalisation between views, more than 4 channels per call, per-cell view directions, GeoTIFF I/O.
 """
-import math
 import numbers
 
 import torch
 
 from . import _lib as L
-from . import camera
 from . import functions as Fn
-from .orthophoto import _image, _on_grid
+from .gridwalk import GridWalk
+from .orthophoto import _image, _sensor_dirs
+from .visibility import NODATA as VIS_NODATA, _on_grid, _zmax
 
 NODATA, OUTSIDE, OCCLUDED, USED, NONFINITE = (L.BN_GATHER_NODATA, L.BN_GATHER_OUTSIDE, L.BN_GATHER_OCCLUDED, L.BN_MOSAIC_USED,
                                               L.BN_MOSAIC_NONFINITE)
 STATES = ("nodata", "outside", "occluded", "used", "nonfinite")
 Q20 = 1 << 20
-
-
-def _view_dirs(name, view_dirs, K):
-    d = torch.as_tensor(view_dirs)
-    if not d.is_floating_point() or tuple(d.shape) != (K, 3):
-        raise ValueError(f"{name}: view_dirs must be ({K}, 3) floats (east, north, up), one direction per view")
-    d = d.detach().to(device="cpu", dtype=torch.float64)
-    if not bool(torch.isfinite(d).all()) or not bool((d[:, 2] > 0).all()):
-        raise ValueError(f"{name}: every view_dir must be finite and point upwards, from the surface towards the sensor")
-    return d
 
 
 def nadir_ranks(view_dirs):
@@ -77,15 +68,11 @@ def orthomosaic(views, dsm, grid, zone, south=False, occlusion=True, eps=0.0, vi
     there), "visible" (K, H, W) uint8 as grid_visibility's (None without occlusion), "view_dirs" float64 (K, 3) on the host or None,
     "rank" [K ints], "counts" {"nodata", "outside", "occluded", "used", "nonfinite": [K ints]}, "consistency": q / (cells C 2^20),
     NaN without a cell seen twice, "cells", "skipped"}."""
-    from .distributed import allreduce_, gather_rows, row_band, world_info
-    from .visibility import NODATA as VIS_NODATA, _zmax
     name = "orthomosaic"
     views = list(views)
     K = len(views)
     if not 1 <= K <= L.BN_MOSAIC_MAX_VIEWS:
         raise ValueError(f"{name}: {K} views (1 to {L.BN_MOSAIC_MAX_VIEWS})")
-    if layout not in ("image", "planes"):
-        raise ValueError(f"{name}: layout {layout!r} ('image' or 'planes')")
     taken = []
     for k, view in enumerate(views):
         if len(view) != 4:
@@ -101,60 +88,35 @@ def orthomosaic(views, dsm, grid, zone, south=False, occlusion=True, eps=0.0, vi
         raise ValueError(f"{name}: mode {mode!r} ('bilinear' or 'nearest')")
     zone, south = Fn._zone(name, zone, south)
     H, W = dsm.shape
-    _, world = world_info(group)
-    rows = row_band(name, H, rows, group)
+    walk = GridWalk(name, H, rows, group)
     res, eps, _ = Fn._vis_scalars(name, grid.resolution, eps, 0.0)
-    if view_dirs is not None:
-        view_dirs = _view_dirs(name, view_dirs, K)
-    if alt_bounds is not None:
-        alt_bounds = (float(alt_bounds[0]), float(alt_bounds[1]))
-        if not (math.isfinite(alt_bounds[0]) and math.isfinite(alt_bounds[1]) and alt_bounds[1] > alt_bounds[0]):
-            raise ValueError(f"{name}: alt_bounds {alt_bounds} must be finite and ascending")
     if rank is not None:
         rank = list(rank)
         if len(rank) != K or any(isinstance(r, bool) or not isinstance(r, numbers.Integral) or not -(1 << 31) <= r < 1 << 31 for r in rank):
             raise ValueError(f"{name}: rank {rank} is not {K} integers, one per view")
         rank = [int(r) for r in rank]
     Fn._maybe(name, colrow, "colrow", Fn.F64, (K, H, W, 2))
-    Fn._on_device(name, dsm, colrow, *[t[0] for t in taken])
-    dev = dsm.device
-    if occlusion and view_dirs is None:
-        if alt_bounds is None:
-            known = dsm[torch.isfinite(dsm)]
-            if known.numel() == 0:
-                raise ValueError(f"{name}: the {H} x {W} DSM has no finite cell to take alt_bounds from")
-            lo, hi = float(known.min()), float(known.max())
-            alt_bounds = (lo, max(hi, lo + 1.0))
-        view_dirs = _view_dirs(name, torch.stack([torch.as_tensor(camera.view_direction(t[4], zone, south, *alt_bounds, device=dev))
-                                                  for t in taken]), K)
+    view_dirs = _sensor_dirs(name, "view_dirs", view_dirs, [t[4] for t in taken], dsm, zone, south, alt_bounds, occlusion,
+                             (dsm, colrow, *[t[0] for t in taken]))
     if rank is None:
         rank = list(range(K)) if view_dirs is None else nadir_ranks(view_dirs)
-    alone = world == 1 and rows != (0, H)                  # a band without a group: the other rows are unseen
-    make = lambda shape, dtype, value: torch.full(shape, value, dtype=dtype, device=dev) if alone else \
-        torch.empty(shape, dtype=dtype, device=dev)
+    dev, nan = dsm.device, float("nan")                     # outside a lone band: no view saw the cell
     totals = torch.zeros((8 * K + 3,), dtype=torch.int64, device=dev)          # counts (K, 5), sums (3), grid_visibility's (K, 3)
     counts, sums = totals[:5 * K].view(K, 5), totals[5 * K:5 * K + 3]
     visible = None
     if occlusion:
-        visible, _, _ = Fn.grid_visibility(dsm, res, view_dirs, eps, _zmax(dsm), rows=rows, vis=make((K, H, W), Fn.U8, VIS_NODATA),
-                                           counts=totals[5 * K + 3:].view(K, 3))
+        visible, _, _ = Fn.grid_visibility(dsm, res, view_dirs, eps, _zmax(dsm), rows=walk.rows, counts=totals[5 * K + 3:].view(K, 3),
+                                           vis=walk.buffer((K, H, W), Fn.U8, VIS_NODATA, dev))
     table = [(t[0], t[1], t[2], t[3], None if visible is None else visible[k], rank[k], t[4]) for k, t in enumerate(taken)]
-    nan = float("nan")
-    out = Fn.grid_mosaic(table, C, dsm, grid.xoff, grid.yoff, res, zone, south, rows=rows, mode=mode, colrow=colrow,
-                         count=make((H, W), Fn.U8, 0), best=make((H, W), Fn.I32, -1), best_val=make((C, H, W), Fn.F32, nan),
-                         mean=make((C, H, W), Fn.F32, nan), std=make((C, H, W), Fn.F32, nan), counts=counts, sums=sums)
-    count, best = out["count"], out["best"]
-    maps = [out["best_val"], out["mean"], out["std"]]
-    if world > 1:
-        band = lambda t: gather_rows(t[rows[0]:rows[1]].contiguous(), group)
-        planes = lambda t: band(t.transpose(0, 1)).transpose(0, 1).contiguous()
-        maps = [planes(t) for t in maps]
-        if maps[0].shape[1] != H:
-            raise ValueError(f"{name}: the ranks' bands cover {maps[0].shape[1]} rows of {H}")
-        count, best = band(count), band(best)
-        if occlusion:
-            visible = planes(visible)
-        allreduce_(totals, group=group)
+    out = Fn.grid_mosaic(table, C, dsm, grid.xoff, grid.yoff, res, zone, south, rows=walk.rows, mode=mode, colrow=colrow,
+                         count=walk.buffer((H, W), Fn.U8, 0, dev), best=walk.buffer((H, W), Fn.I32, -1, dev),
+                         best_val=walk.buffer((C, H, W), Fn.F32, nan, dev), mean=walk.buffer((C, H, W), Fn.F32, nan, dev),
+                         std=walk.buffer((C, H, W), Fn.F32, nan, dev), counts=counts, sums=sums)
+    maps = [walk.join(out[k], 1) for k in ("best_val", "mean", "std")]
+    count, best = walk.join(out["count"]), walk.join(out["best"])
+    if occlusion:
+        visible = walk.join(visible, 1)
+    walk.merge(totals)
     per_view = counts.tolist()
     cells, q, skipped = sums.tolist()
     return {"best_rgb": maps[0], "mean": maps[1], "std": maps[2], "count": count, "best": best, "visible": visible,

@@ -20,8 +20,8 @@ this order, NODATA (0: its pixel is NaN - a NaN or infinite cell of the DSM, a p
 <= W - 1 and 0 <= row <= H - 1), OCCLUDED (2: grid_visibility towards the sensor says another cell is in the way) or KEPT (3);
 only kept cells carry values, the others are NaN.  Bilinear values are formed in float64 from the four taps, every operation
 rounded on its own, and cast to float32; a NaN tap propagates.  Nearest copies the pixel's 32 bits.  Everything depends on the
-inputs alone: not on row bands (rows=) or on how many GPUs shared the grid (the bands are gathered, the counts merge by one SUM
-all-reduce).
+inputs alone: not on row bands (rows=) or on how many GPUs shared the grid (gridwalk.py: the bands are gathered, the counts merge
+by one SUM all-reduce).
 
 ONE direction serves the whole scene in the occlusion test (view_direction at the image's centre pixel): over a scene of a few
 hundred metres a satellite's rays are parallel to well within a cell.  A NaN cell never blocks, so a DSM with holes lets the
@@ -41,6 +41,8 @@ import torch
 from . import _lib as L
 from . import camera
 from . import functions as Fn
+from .gridwalk import GridWalk
+from .visibility import NODATA as VIS_NODATA, _on_grid, _zmax
 
 NODATA, OUTSIDE, OCCLUDED, KEPT = L.BN_GATHER_NODATA, L.BN_GATHER_OUTSIDE, L.BN_GATHER_OCCLUDED, L.BN_GATHER_KEPT
 STATES = ("nodata", "outside", "occluded", "kept")
@@ -60,12 +62,6 @@ def _image(name, image, H_img, W_img, layout):
     if not 1 <= C <= L.BN_GATHER_MAX_CHANNELS:
         raise ValueError(f"{name}: image {tuple(image.shape)} has {C} channels at {H_img} x {W_img} pixels (1 to {L.BN_GATHER_MAX_CHANNELS})")
     return image, C, ((W_img * C, C, 1) if layout == "image" else (W_img, 1, H_img * W_img))
-
-
-def _on_grid(name, dsm, grid):
-    Fn._need(name, dsm, **Fn.VIS_DSM)
-    if tuple(dsm.shape) != (grid.height, grid.width):
-        raise ValueError(f"{name}: dsm {tuple(dsm.shape)} is not on the grid of {grid.height} x {grid.width} cells")
 
 
 def _counts(states, skipped=None):
@@ -129,14 +125,41 @@ def sample_image(image, H_img, W_img, colrow, visible=None, mode="bilinear", lay
     return {"ortho": out.reshape((C,) + cells), "state": state.reshape(cells), "counts": _counts(counts.tolist())}
 
 
-def _view_dir(name, view_dir):
-    d = torch.as_tensor(view_dir)
-    if not d.is_floating_point() or d.numel() != 3:
-        raise ValueError(f"{name}: view_dir must be 3 floats (east, north, up)")
-    d = d.detach().to(device="cpu", dtype=torch.float64).reshape(3)
-    if not bool(torch.isfinite(d).all()) or not float(d[2]) > 0:
-        raise ValueError(f"{name}: view_dir {d.tolist()} must be finite and point upwards, from the surface towards the sensor")
-    return d
+def _sensor_dirs(name, noun, given, rpcs, dsm, zone, south, alt_bounds, occlusion, on_device):
+    """The directions from the surface towards the sensors of the K `rpcs`, one for the whole scene each -> float64 (K, 3) on the
+    host, or None without occlusion and without `given`.  given: the caller's `noun` - "view_dir": any 3 floats, "view_dirs": (K, 3)
+    floats - else camera.view_direction of every rpc between alt_bounds = (alt_lo, alt_hi), by default the minimum and maximum of
+    the finite cells (at least a metre apart).  Every direction must be finite and point upwards.  The arguments are refused first,
+    then - the caller's last host-side check - a host tensor among `on_device`, then what reads the device: a DSM without a finite
+    cell, a derived direction."""
+    K, one = len(rpcs), noun == "view_dir"
+
+    def checked(d):
+        d = torch.as_tensor(d)
+        if not d.is_floating_point() or (d.numel() != 3 if one else tuple(d.shape) != (K, 3)):
+            shape = "3 floats (east, north, up)" if one else f"({K}, 3) floats (east, north, up), one direction per view"
+            raise ValueError(f"{name}: {noun} must be {shape}")
+        d = d.detach().to(device="cpu", dtype=torch.float64).reshape(K, 3)
+        if not bool(torch.isfinite(d).all()) or not bool((d[:, 2] > 0).all()):
+            raise ValueError(f"{name}: {f'view_dir {d[0].tolist()}' if one else 'every view_dir'} must be finite and point upwards, from "
+                             "the surface towards the sensor")
+        return d
+    if given is not None:
+        given = checked(given)
+    if alt_bounds is not None:
+        alt_bounds = (float(alt_bounds[0]), float(alt_bounds[1]))
+        if not (math.isfinite(alt_bounds[0]) and math.isfinite(alt_bounds[1]) and alt_bounds[1] > alt_bounds[0]):
+            raise ValueError(f"{name}: alt_bounds {alt_bounds} must be finite and ascending")
+    Fn._on_device(name, *on_device)
+    if given is not None or not occlusion:
+        return given
+    if alt_bounds is None:
+        known = dsm[torch.isfinite(dsm)]
+        if known.numel() == 0:
+            raise ValueError(f"{name}: the {dsm.shape[0]} x {dsm.shape[1]} DSM has no finite cell to take alt_bounds from")
+        lo, hi = float(known.min()), float(known.max())
+        alt_bounds = (lo, max(hi, lo + 1.0))
+    return checked(torch.stack([torch.as_tensor(camera.view_direction(r, zone, south, *alt_bounds, device=dsm.device)) for r in rpcs]))
 
 
 @torch.no_grad()
@@ -156,8 +179,6 @@ def orthophoto(image, H_img, W_img, rpc, dsm, grid, zone, south=False, occlusion
     -> {"ortho" (C, H, W) float32, NaN where the state is not KEPT, "state" (H, W) uint8 in {NODATA 0, OUTSIDE 1, OCCLUDED 2,
     KEPT 3}, "colrow" (H, W, 2) float64, "visible" (H, W) uint8 as grid_visibility's (None without occlusion), "counts"
     {"skipped", "nodata", "outside", "occluded", "kept"}, "view_dir" float64 (3,) on the host (None without occlusion)}."""
-    from .distributed import allreduce_, gather_rows, row_band, world_info
-    from .visibility import NODATA as VIS_NODATA, _zmax
     name = "orthophoto"
     image, C, strides = _image(name, image, H_img, W_img, layout)
     _on_grid(name, dsm, grid)
@@ -165,50 +186,29 @@ def orthophoto(image, H_img, W_img, rpc, dsm, grid, zone, south=False, occlusion
         raise ValueError(f"{name}: mode {mode!r} ('bilinear' or 'nearest')")
     zone, south = Fn._zone(name, zone, south)
     H, W = dsm.shape
-    _, world = world_info(group)
-    rows = row_band(name, H, rows, group)
+    walk = GridWalk(name, H, rows, group)
+    rows = walk.rows
     res, eps, _ = Fn._vis_scalars(name, grid.resolution, eps, 0.0)
-    if view_dir is not None:
-        view_dir = _view_dir(name, view_dir)
-    if alt_bounds is not None:
-        alt_bounds = (float(alt_bounds[0]), float(alt_bounds[1]))
-        if not (math.isfinite(alt_bounds[0]) and math.isfinite(alt_bounds[1]) and alt_bounds[1] > alt_bounds[0]):
-            raise ValueError(f"{name}: alt_bounds {alt_bounds} must be finite and ascending")
-    Fn._on_device(name, image, dsm)
-    dev = dsm.device
+    dirs = _sensor_dirs(name, "view_dir", view_dir, [rpc], dsm, zone, south, alt_bounds, occlusion, (image, dsm))
+    dev, nan = dsm.device, float("nan")                     # outside a lone band: NODATA and NaN
+    counts = torch.zeros((8,), dtype=torch.int64, device=dev)          # skipped, the four states, grid_visibility's three
+    colrow, _ = Fn.grid_pixels(rpc, dsm, grid.xoff, grid.yoff, res, zone, south, rows=rows, colrow=walk.buffer((H, W, 2), Fn.F64, nan, dev),
+                               counts=counts[0:1])
     visible = None
     if occlusion:
-        if view_dir is None:
-            if alt_bounds is None:
-                known = dsm[torch.isfinite(dsm)]
-                if known.numel() == 0:
-                    raise ValueError(f"{name}: the {H} x {W} DSM has no finite cell to take alt_bounds from")
-                lo, hi = float(known.min()), float(known.max())
-                alt_bounds = (lo, max(hi, lo + 1.0))
-            view_dir = _view_dir(name, camera.view_direction(rpc, zone, south, *alt_bounds, device=dev))
-    alone = world == 1 and rows != (0, H)                  # a band without a group: the other rows are NODATA and NaN
-    make = lambda shape, dtype, value: torch.full(shape, value, dtype=dtype, device=dev) if alone else \
-        torch.empty(shape, dtype=dtype, device=dev)
-    counts = torch.zeros((8,), dtype=torch.int64, device=dev)          # skipped, the four states, grid_visibility's three
-    colrow, _ = Fn.grid_pixels(rpc, dsm, grid.xoff, grid.yoff, res, zone, south, rows=rows, colrow=make((H, W, 2), Fn.F64, float("nan")),
-                               counts=counts[0:1])
-    if occlusion:
-        visible, _, _ = Fn.grid_visibility(dsm, res, view_dir[None], eps, _zmax(dsm), rows=rows, vis=make((1, H, W), Fn.U8, VIS_NODATA),
+        visible, _, _ = Fn.grid_visibility(dsm, res, dirs, eps, _zmax(dsm), rows=rows, vis=walk.buffer((1, H, W), Fn.U8, VIS_NODATA, dev),
                                            counts=counts[5:8].reshape(1, 3))
         visible = visible[0]
     ortho, state, _ = Fn.image_gather(image, H_img, W_img, C, strides, colrow, visible, cells=(rows[0] * W, rows[1] * W), mode=mode,
-                                      out=make((C, H, W), Fn.F32, float("nan")), state=make((H, W), Fn.U8, NODATA), counts=counts[1:5])
-    if world > 1:
-        band = lambda t: gather_rows(t[rows[0]:rows[1]].contiguous(), group)
-        ortho = band(ortho.transpose(0, 1)).transpose(0, 1).contiguous()
-        if ortho.shape[1] != H:
-            raise ValueError(f"{name}: the ranks' bands cover {ortho.shape[1]} rows of {H}")
-        state, colrow = band(state), band(colrow)
-        if occlusion:
-            visible = band(visible)
-        allreduce_(counts, group=group)
+                                      out=walk.buffer((C, H, W), Fn.F32, nan, dev), state=walk.buffer((H, W), Fn.U8, NODATA, dev),
+                                      counts=counts[1:5])
+    ortho, state, colrow = walk.join(ortho, 1), walk.join(state), walk.join(colrow)
+    if occlusion:
+        visible = walk.join(visible)
+    walk.merge(counts)
     c = counts.tolist()
-    return {"ortho": ortho, "state": state, "colrow": colrow, "visible": visible, "counts": _counts(c[1:5], c[0]), "view_dir": view_dir}
+    return {"ortho": ortho, "state": state, "colrow": colrow, "visible": visible, "counts": _counts(c[1:5], c[0]),
+            "view_dir": None if dirs is None else dirs[0]}
 
 
 @torch.no_grad()

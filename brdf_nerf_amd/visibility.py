@@ -16,7 +16,7 @@ never a running sum), reads the cell it is over and is BLOCKED (0) if that cell'
 grid makes the start VISIBLE (1); a start without data - a NaN or infinite cell, a point that is not finite or not over the grid -
 is NODATA (2).  A NaN cell never blocks.  Everything is float64 with each operation rounded on its own, so every bit of `visible`,
 `hit` and `counts` depends on the grid, the starts and the directions alone: not on row bands (rows=), on how the directions are
-split over launches (dir_tile=), or on how many GPUs shared the grid (the bands are gathered, the counts merge by one SUM all-reduce).
+split over launches (dir_tile=), or on how many GPUs shared the grid (gridwalk.py: bands gathered, counts merged by one SUM all-reduce).
 
 The sun's shadow mask: pass the sun direction.  The view-occlusion mask - "this view saw this cell" - is the same march towards
 the sensor: pass -rays[:, 3:6] of the view (one direction per call: the mean of the view's rays, or any ray's; over a scene of a
@@ -39,6 +39,7 @@ import torch
 
 from . import _lib as L
 from . import functions as Fn
+from .gridwalk import GridWalk
 
 BLOCKED, VISIBLE, NODATA = L.BN_VIS_BLOCKED, L.BN_VIS_VISIBLE, L.BN_VIS_NODATA
 
@@ -66,40 +67,29 @@ def grid_visibility(dsm, resolution, dirs, eps=0.0, rows=None, group=None, want_
     dir_tile: directions per call of the entry (None: all K in one).
     -> {"visible" (K, H, W) uint8 in {0 blocked, 1 visible, 2 nodata}, "counts" (K, 3) int64 on the host = (blocked, visible,
     nodata)} (+ "hit" (K, H, W) int32: the flat index of the first blocking cell, or -1)."""
-    from .distributed import allreduce_, gather_rows, row_band, world_info
     name = "grid_visibility"
     Fn._need(name, dsm, **Fn.VIS_DSM)
     dirs = Fn._vis_dirs(name, dirs)
     H, W = dsm.shape
     K = dirs.shape[0]
-    _, world = world_info(group)
-    rows = row_band(name, H, rows, group)
+    walk = GridWalk(name, H, rows, group)
     step = K if dir_tile is None else int(dir_tile)
     if step < 1:
         raise ValueError(f"{name}: dir_tile {dir_tile} must be at least 1")
     Fn._vis_scalars(name, resolution, eps, 0.0)
     Fn._on_device(name, dsm)
     zmax = _zmax(dsm)
-    alone = world == 1 and rows != (0, H)                  # a band without a group: the other rows are NODATA and -1
-    buffer = lambda dtype, value: torch.full((K, H, W), value, dtype=dtype, device=dsm.device) if alone else \
-        torch.empty((K, H, W), dtype=dtype, device=dsm.device)
-    vis = buffer(torch.uint8, NODATA)
-    hit = buffer(torch.int32, -1) if want_hit else None
+    vis = walk.buffer((K, H, W), torch.uint8, NODATA, dsm.device)         # outside a lone band: NODATA and -1
+    hit = walk.buffer((K, H, W), torch.int32, -1, dsm.device) if want_hit else None
     counts = torch.zeros((K, 3), dtype=torch.int64, device=dsm.device)
     for k0 in range(0, K, step):
         k1 = min(K, k0 + step)
-        Fn.grid_visibility(dsm, resolution, dirs[k0:k1], eps, zmax, rows=rows, vis=vis[k0:k1], hit=None if hit is None else hit[k0:k1],
-                           counts=counts[k0:k1])
-    if world > 1:
-        band = lambda t: gather_rows(t[:, rows[0]:rows[1]].transpose(0, 1).contiguous(), group)
-        vis = band(vis)
-        if vis.shape[0] != H:
-            raise ValueError(f"{name}: the ranks' bands cover {vis.shape[0]} rows of {H}")
-        vis = vis.transpose(0, 1).contiguous()
-        if want_hit:
-            hit = band(hit).transpose(0, 1).contiguous()
-        allreduce_(counts, group=group)
-    return _result(vis, hit, counts, want_hit)
+        Fn.grid_visibility(dsm, resolution, dirs[k0:k1], eps, zmax, rows=walk.rows, vis=vis[k0:k1],
+                           hit=None if hit is None else hit[k0:k1], counts=counts[k0:k1])
+    vis = walk.join(vis, 1)
+    if want_hit:
+        hit = walk.join(hit, 1)
+    return _result(vis, hit, walk.merge(counts), want_hit)
 
 
 def _on_grid(name, dsm, grid):
