@@ -21,6 +21,7 @@ from .ortho import OrthoAccumulator, ortho_image  # noqa: F401
 from .visibility import grid_visibility, point_visibility, view_visibility  # noqa: F401
 from .orthophoto import world_pixels, grid_pixels, sample_image, orthophoto, ortho_psnr  # noqa: F401
 from .mosaic import orthomosaic  # noqa: F401
+from .raycast import cast_rays, grid_to_view, surface_priors  # noqa: F401
 from . import camera  # noqa: F401
 from .camera import Rpc, view_rays, scene_bounds, ray_table, utm_zone, sun_direction, depth_priors, nearest_lines  # noqa: F401
 from .camera import ecef_geodetic  # noqa: F401
@@ -35,5 +36,6 @@ __all__ = ["SpSBRDFNeRF", "load_model", "render_rays", "inference", "get_z_vals"
            "ray_maps", "point_normals", "depth_normals", "view_maps", "OrthoAccumulator", "ortho_image",
            "grid_visibility", "point_visibility", "view_visibility",
            "world_pixels", "grid_pixels", "sample_image", "orthophoto", "ortho_psnr", "orthomosaic",
+           "cast_rays", "grid_to_view", "surface_priors",
            "camera", "Rpc", "view_rays", "scene_bounds", "ray_table", "utm_zone", "sun_direction", "depth_priors",
            "nearest_lines", "ecef_geodetic"]

@@ -17,7 +17,7 @@ include/brdfnerf_hip.h ("The rays of a satellite view") and runs in brdf_nerf_am
   depth_priors       load_depth_data (:401-548) of one view from its tie points, paired by pixel: depths, weights, valid_depth,
                      depth_std, the padded rays and the normals (bn_tie_owner, bn_tie_priors, one lane per tie point)
   ray_table          the views of a scene concatenated into a RayTable (load_data, :311-394, and with priors= load_depth_data:
-                     load_train_split without its file readers)
+                     load_train_split without its file readers; a view's priors may also be a surface model, raycast.surface_priors)
   utm_zone           the zone of a point, with the Norway and Svalbard exceptions (utm.latlon_to_zone_number)
   sun_direction      get_sun_dirs (:561-576)
 
@@ -545,12 +545,20 @@ def ray_table(views, images, center, range=None, cs="utm", zone=None, south=Fals
     valid_depth = 0 rows.  A view's "H", "W" are its ray grid - the image AFTER its "downscale"; the tie points of a downscaled
     view are at full resolution, which the view names as "full_H", "full_W" (their resize must be H x W).  priors=None: the
     table without depth columns.  want_normals (with priors): the table also gains depth_priors' normals and valid_normal - what
-    FusedTrainer's nr_spv_type 2 / 3 read; a view with None has the normal (0, 0, 1) and valid_normal = 0."""
+    FusedTrainer's nr_spv_type 2 / 3 read; a view with None has the normal (0, 0, 1) and valid_normal = 0.
+    A view's priors may also be {"dsm": (h, w) float32 on the device, "grid": dsm.Grid} with an optional "weight" (default 1): a
+    surface model in place of tie points - its columns are raycast.surface_priors of the view's own rays (stdscale, margin,
+    std_span as above).  It needs cs='utm'; with want_normals such a view has the normal (0, 0, 1) and valid_normal = 0."""
     from .raytable import RayTable
     if len(views) != len(images) or not views:
         raise ValueError(f"ray_table: {len(views)} views and {len(images)} images")
     if priors is not None and len(priors) != len(views):
         raise ValueError(f"ray_table: {len(views)} views and {len(priors)} priors")
+    if priors is not None and cs != "utm":
+        for i, p in enumerate(priors):
+            if isinstance(p, dict) and ("dsm" in p or "grid" in p):
+                raise ValueError(f"ray_table: the surface prior of view {i} needs cs='utm', not {cs!r}: a surface model is cast in a "
+                                 "frame whose world axes are (east, north, up)")
     tables, cols = [], {"depths": [], "valid_depth": [], "depth_std": []}
     if want_normals:
         if priors is None:
@@ -571,6 +579,17 @@ def ray_table(views, images, center, range=None, cs="utm", zone=None, south=Fals
             pr = {"depths": torch.zeros((H * W, 2), device=rays.device), "valid_depth": torch.zeros((H * W,), device=rays.device),
                   "depth_std": torch.zeros((H * W,), device=rays.device)}
             if want_normals:
+                pr["normals"] = torch.tensor([0.0, 0.0, 1.0], device=rays.device).repeat(H * W, 1)
+                pr["valid_normal"] = torch.zeros((H * W,), device=rays.device)
+        elif "dsm" in priors[i] or "grid" in priors[i]:
+            from .dsm import SceneFrame
+            from .raycast import surface_priors
+            missing = [k for k in ("dsm", "grid") if k not in priors[i]]
+            if missing:
+                raise ValueError(f"ray_table: the surface prior of view {i} lacks {missing}")
+            pr = surface_priors(rays, SceneFrame(*_frame(center, range, cs), cs="utm"), priors[i]["dsm"], priors[i]["grid"],
+                                weight=priors[i].get("weight", 1.0), stdscale=stdscale, margin=margin, std_span=std_span)
+            if want_normals:                   # a raster's normals are not served: the view's rows carry no normal target
                 pr["normals"] = torch.tensor([0.0, 0.0, 1.0], device=rays.device).repeat(H * W, 1)
                 pr["valid_normal"] = torch.zeros((H * W,), device=rays.device)
         else:

@@ -1636,3 +1636,53 @@ def grid_mosaic(views, C_, dsm, xoff, yoff, res, zone, south, rows=None, mode="b
                                        GATHER_MODES[mode], _p(colrow), _p(count), _p(best), _p(best_val), _p(mean), _p(std),
                                        _p(counts), _p(sums), _stream()), "bn_grid_mosaic")
     return {"count": count, "best": best, "best_val": best_val, "mean": mean, "std": std, "counts": counts, "sums": sums}
+
+
+def _cast_scalars(name, center, rng, xoff, yoff, res, zmax):
+    center = tuple(float(v) for v in center)
+    rng, xoff, yoff, res, zmax = float(rng), float(xoff), float(yoff), float(res), float(zmax)
+    if len(center) != 3 or not all(math.isfinite(v) for v in center):
+        raise ValueError(f"{name}: centre {center} must be 3 finite numbers")
+    if not (rng > 0 and math.isfinite(rng)):
+        raise ValueError(f"{name}: range {rng} must be positive and finite")
+    if not (res > 0 and math.isfinite(res)):
+        raise ValueError(f"{name}: resolution {res} must be positive and finite")
+    if not (math.isfinite(xoff) and math.isfinite(yoff)):
+        raise ValueError(f"{name}: grid origin ({xoff}, {yoff}) is not finite")
+    if math.isnan(zmax):
+        raise ValueError(f"{name}: zmax is NaN")
+    return center, rng, xoff, yoff, res, zmax
+
+
+def cast_rays(rays, center, rng, dsm, xoff, yoff, res, zmax=float("inf"), depth=None, state=None, cell=None, nan_cells=None,
+              counts=None, want_cell=True, want_nan=True):
+    """The depth at which rays meet a height grid (bn_cast_rays): rays (R, >= 8) float32 rows with unit inner stride (o, d, near,
+    far), center (3 floats) and rng the normalisation of a UTM scene, dsm (H, W) float32 with its Grid's origin and resolution.
+    depth (R,) float32, state (R,) uint8, cell (R,) int32, nan_cells (R,) int32 and counts (5,) int64 may be given - slices of a
+    view's buffers, say - and counts are accumulated into; cell / nan_cells are made unless want_cell / want_nan say otherwise.
+    -> depth, state, cell or None, nan_cells or None, counts."""
+    name = "cast_rays"
+    rays = _need(name, rays, "rays", F32, ("R", ">=8"), "rows")
+    _need(name, dsm, **VIS_DSM)
+    center, rng, xoff, yoff, res, zmax = _cast_scalars(name, center, rng, xoff, yoff, res, zmax)
+    R = rays.shape[0]
+    if R > (1 << 30):
+        raise ValueError(f"{name}: {R} rays (0 to 2^30)")
+    if R > 1 and rays.stride(0) < 8:
+        rays = rays.contiguous()
+    H, W = dsm.shape
+    dev = dsm.device
+    depth = _out(name, depth, "depth", F32, (R,), dev, torch.empty)
+    state = _out(name, state, "state", U8, (R,), dev, torch.empty)
+    if cell is not None or want_cell:
+        cell = _out(name, cell, "cell", I32, (R,), dev, torch.empty)
+    if nan_cells is not None or want_nan:
+        nan_cells = _out(name, nan_cells, "nan_cells", I32, (R,), dev, torch.empty)
+    counts = _out(name, counts, "counts", I64, (5,), dev)
+    _on_device(name, rays, dsm, depth, state, cell, nan_cells, counts)
+    if R:
+        with torch.cuda.device(dev):
+            L.check(L.lib().bn_cast_rays(C.c_void_p(rays.data_ptr()), rays.stride(0) if R > 1 else rays.shape[1], R,
+                                         (C.c_double * 3)(*center), rng, _p(dsm), H, W, xoff, yoff, res, zmax, _p(depth), _p(state),
+                                         _p(cell), _p(nan_cells), _p(counts), _stream()), "bn_cast_rays")
+    return depth, state, cell, nan_cells, counts

@@ -181,7 +181,7 @@ def normal_angle_mae(dsm, gt, resolution, mask=None, border="reference"):
 @torch.no_grad()
 def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=None, grid=None, dsm_mask=None, group=None,
                window=3, layout="reference", radius=1, footprint="disc", resolution=0.5, register="z", sun_dir=None, shadow_dsm=None,
-               shadow_eps=0.0, **render_kw):
+               shadow_eps=0.0, cast_dsm=None, **render_kw):
     """The reference's evaluation line of one view (eval.py:467-479) in one call: psnr, psnr_scl, ssim, ssim_scl and - with a
     `frame` - the DSM, and with `gt_dsm` on that grid mae, mae_in, mae_out (altitude_mae) and mae_nr (normal_angle_mae).
     rays (H W, >= 8), rgbs (H W, 3) the ground truth, mask the view's valid pixels ((H, W) or (H W,)), dsm_mask the DSM's
@@ -200,6 +200,11 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
     (H W,) uint8 (0 shadowed, 1 sunlit, 2 no data), "shadow_fraction" = shadowed / (shadowed + sunlit) over the pixels the mask
     keeps (NaN without one), "psnr_sunlit" and "psnr_shadow" = image_psnr under mask AND visibility == 1 / == 0, with upstream's
     whole-target normaliser; a class without a pixel gives -1.  sun_dir=None: nothing changes, no key and no bit.
+    cast_dsm (needs a 'utm' frame and `grid`): a ground-truth surface model (grid.height, grid.width) float32 seen from the very
+    pixels (raycast.cast_rays): "depth_gt" (H W,) float32, NaN where a ray met nothing, "cast_state" (H W,) uint8, "depth_mae" =
+    the mean of |depth - depth_gt| range, in metres along the ray, and "alt_mae_view" = the mean of |altitude_image(rays, depth) -
+    altitude_image(rays, depth_gt)|, both over the pixels the mask keeps and that were hit, from an int64 sum of round(|e| 2^20)
+    and a count - independent of order and ranks; NaN without such a pixel.  cast_dsm=None: no key and no bit changes.
     -> {"psnr", "psnr_scl", "ssim", "ssim_scl", "ssim_skipped", "ssim_sums", "rgb", "depth"} (+ "dsm", "count", "grid",
     "skipped" with a frame; + "mae", "mae_in", "mae_out", "mae_nr", "mae_nr_in", "mae_nr_out", "shift" with gt_dsm)."""
     from .distributed import allreduce_, row_band
@@ -223,6 +228,14 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
         Fn._vis_scalars("score_view", resolution, shadow_eps, 0.0)
         if shadow_dsm is not None and grid is not None and tuple(torch.as_tensor(shadow_dsm).shape) != (grid.height, grid.width):
             raise ValueError(f"score_view: shadow_dsm {tuple(torch.as_tensor(shadow_dsm).shape)} is not on the grid of "
+                             f"{grid.height} x {grid.width} cells")
+    if cast_dsm is not None:
+        if frame is None or grid is None:
+            raise ValueError("score_view: cast_dsm needs the scene's frame (frame=) and the grid the surface model is on (grid=)")
+        if frame.cs == "ecef":
+            raise ValueError("score_view: cast_dsm is not served on an 'ecef' frame: its world axes are not (east, north, up)")
+        if tuple(torch.as_tensor(cast_dsm).shape) != (grid.height, grid.width):
+            raise ValueError(f"score_view: cast_dsm {tuple(torch.as_tensor(cast_dsm).shape)} is not on the grid of "
                              f"{grid.height} x {grid.width} cells")
     check_window(window, H, W)
     view = render_image(models, args, rays, None, keys=("rgb", "depth"), group=group, **render_kw)
@@ -256,7 +269,30 @@ def score_view(models, args, rays, rgbs, H, W, mask=None, frame=None, gt_dsm=Non
                        mae_nr=nr["mae_nr"], mae_nr_in=nr["mae_nr_in"], mae_nr_out=nr["mae_nr_out"])
         if sun_dir is not None:
             res.update(_shadow_split(rays, rgb, rgbs, depth, mask, frame, grid, dsm, gt_dsm, shadow_dsm, sun_dir, shadow_eps, group))
+        if cast_dsm is not None:
+            res.update(_cast_errors(rays, depth, mask, frame, grid, cast_dsm, group))
     return res
+
+
+def _cast_errors(rays, depth, mask, frame, grid, cast_dsm, group):
+    """score_view's cast_dsm keys: the surface model's depth along the view's own rays and the two image-space MAEs."""
+    from .dsm import altitude_image
+    from .raycast import cast_rays
+    rays32 = Fn._f32(rays)
+    cast = cast_rays(rays32, frame, Fn._f32(torch.as_tensor(cast_dsm).to(rays.device)), grid, group=group)
+    depth_gt, hit = cast["depth"], cast["cell"] >= 0
+    keep = hit if mask is None else hit & (torch.as_tensor(mask).to(hit.device).reshape(-1) != 0)
+    if keep.numel() != depth.numel():
+        raise ValueError(f"score_view: mask of {keep.numel()} elements for {depth.numel()} pixels")
+    d = depth.reshape(-1).to(depth_gt.device)
+    errors = {"depth_mae": (d.double() - depth_gt.double()).abs() * frame.range,
+              "alt_mae_view": (altitude_image(rays32, d, frame) - altitude_image(rays32, depth_gt, frame)).abs()}
+    out = {"depth_gt": depth_gt, "cast_state": cast["state"]}
+    for key, e in errors.items():
+        sel = keep & torch.isfinite(e)
+        q = torch.round(torch.where(sel, e, torch.zeros_like(e)) * ANGLE_FIX).to(torch.int64)
+        out[key] = Fn.fixed_mean(int(q.sum()), int(sel.sum()), ANGLE_FIX)
+    return out
 
 
 def _shadow_split(rays, rgb, rgbs, depth, mask, frame, grid, dsm, gt_dsm, shadow_dsm, sun_dir, eps, group):

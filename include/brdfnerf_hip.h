@@ -990,6 +990,56 @@ int bn_grid_visibility(const float *dsm, int32_t H, int32_t W, double res, int32
 int bn_points_visibility(const double *enz, int64_t R, const float *dsm, int32_t H, int32_t W, double xoff, double yoff, double res,
                          const double *dirs, int32_t K, double eps, double zmax, uint8_t *vis, int32_t *hit, long long *counts,
                          void *stream);
+/* Depth of a surface model along a ray (additive to ABI 7): at what depth does a view's ray meet a height grid?  The splats above
+ * take a view to the ground and the march above runs between ground points; this takes the ground to a view: depth priors from a
+ * lidar or an earlier DSM, a per-pixel ground truth of a rendered depth, any raster of the grid seen from the view (gather it
+ * through `cell`).  There is NO upstream counterpart - the reference never intersects a ray with a raster - so the rule is this
+ * project's own and there is nothing to check it against but its statement and the project's other rules.
+ *
+ * Grid.  dsm float32 [H][W], north-up, with xoff, yoff, res as in "Visibility over a surface model"; a cell is a flat-topped column.
+ * Rays.  rays float32 [R] rows of ray_stride >= 8 floats: o[3], d[3], near, far.  Frame: center[3], range of a UTM scene (world axes
+ *   east, north, up).
+ * Everything below is float64 and every operation is rounded on its own (no fused multiply-add).
+ * Point.  p(s) = ((double)o + (double)d * s) * range + center, per component: the expression of the DSM splats, so a cast depth fed
+ *   back to them lands on the surface.
+ * Segment.  P0 = p((double)near), P1 = p((double)far);  u = (P.x - xoff) / res, v = (yoff - P.y) / res, z = P.z for both ends;
+ *   du = u1 - u0, dv = v1 - v0, dz = z1 - z0.  A ray with a non-finite one of u0, v0, z0, u1, v1, z1, or with
+ *   fabs(du) + fabs(dv) > BN_CAST_MAX_SPAN, is BN_CAST_NODATA: depth = NaN, cell = -1, nan_cells = 0.
+ * Walk.  An exact cell walk in the segment parameter lam in [0, 1]: (i, j) = (floor(u0), floor(v0)), lam_in = 0.  Per cell:
+ *     lam_u = ((double)(du > 0 ? i + 1 : i) - u0) / du, or +inf when du == 0 ;  lam_v likewise from j, v0, dv
+ *       (always from the INTEGER line index, never from a running sum)
+ *     m = fmin(lam_u, lam_v) ;  lam_out = fmax(lam_in, fmin(m, 1.0))
+ *   Test.  If 0 <= i < W and 0 <= j < H, h = (double)dsm[j][i].  A NaN h is never hit and is counted (nan_cells += 1).  Otherwise
+ *     z_in = z0 + lam_in * dz ;  z_out = z0 + lam_out * dz
+ *     if z_in <= h:        the ray meets the cell at lam = lam_in: BN_CAST_BELOW if this is the start cell, else BN_CAST_WALL
+ *     else if z_out <= h:  BN_CAST_TOP at lam = fmax(lam_in, fmin((h - z0) / dz, lam_out))
+ *     Both comparisons are <= (a ray that only touches a top at the cell's far edge meets it).  +inf always stops a ray, -inf never.
+ *   Hit.  depth = (float)((double)near + lam * ((double)far - (double)near)), cell = j W + i, stop.
+ *   No hit in this cell.  If m >= 1 the ray is BN_CAST_MISS (depth = NaN, cell = -1), stop.  Otherwise i moves by the sign of du if
+ *     lam_u == m and j by the sign of dv if lam_v == m - BOTH on a tie, so a ray through a corner moves diagonally and the two
+ *     cells that touch it only at the corner are not tested.  If then (i < 0 and du < 0) or (i >= W and du > 0), or likewise j, H
+ *     and dv - outside the grid and moving away from it on that axis - the ray is BN_CAST_MISS, stop.  Then lam_in = lam_out.
+ *   The walk crosses no line beyond the far end, so it ends after at most fabs(du) + fabs(dv) + 3 cells.
+ * zmax is an optimisation argument, as in the visibility entries: with nan_cells == NULL a cell whose fmin(z_in, z_out) > zmax need
+ *   not be loaded.  With zmax >= every non-NaN cell this cannot change a bit; zmax = +inf is the plain rule.  With nan_cells every
+ *   cell of the walk inside the grid is loaded: a NaN cell counts wherever the ray passes it.  A smaller zmax is the caller's error.
+ * Skipping.  The walk only visits cells between the two ends on either axis, so a ray whose ends are both west, east, north or
+ *   south of the grid is BN_CAST_MISS with nan_cells = 0 without a walk; the cells outside the grid are walked without a load.
+ * Outputs, plain stores of the lane's own ray: depth float32 [R]; state uint8 [R]; cell int32 [R] (nullable); nan_cells int32 [R]
+ *   (nullable); counts int64 [5] += the rays of the call per state, in the order of the codes: the CALLER zeroes them, one integer
+ *   atomic per class and block, no float atomic.  Every bit depends on the ray, the frame and the raster alone - not on blocks, on
+ *   how the rays are cut into calls, or on the number of ranks (the counts of calls or ranks add up).  R == 0 launches nothing.
+ * Refused (BN_EINVAL, nothing launched, buffers untouched): NULL rays, center, dsm, depth, state or counts; R < 0 or over 2^30; H or
+ * W < 1, or H W > 2^30; ray_stride < 8; res or range not positive and finite; a non-finite centre or grid origin; a NaN zmax. */
+#define BN_CAST_TOP 0
+#define BN_CAST_WALL 1
+#define BN_CAST_MISS 2
+#define BN_CAST_NODATA 3
+#define BN_CAST_BELOW 4
+#define BN_CAST_MAX_SPAN 65536
+int bn_cast_rays(const float *rays, int64_t ray_stride, int64_t R, const double *center, double range, const float *dsm, int32_t H,
+                 int32_t W, double xoff, double yoff, double res, double zmax, float *depth, uint8_t *state, int32_t *cell,
+                 int32_t *nan_cells, long long *counts, void *stream);
 /* Orthophoto of an observed image (additive to ABI 7): every cell of a surface model is taken to the pixel of a satellite image
  * that saw it, and the image - or any per-pixel raster in image geometry - is gathered there.  The ortho entries above splat a
  * VIEW's rays into cells; this is the opposite direction.  There is NO upstream counterpart - the reference never orthorectifies
