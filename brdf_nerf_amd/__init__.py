@@ -19,6 +19,7 @@ from .fill import fill_holes, apply_fill  # noqa: F401
 from .maps import ray_maps, point_normals, depth_normals, view_maps  # noqa: F401
 from .ortho import OrthoAccumulator, ortho_image  # noqa: F401
 from .visibility import grid_visibility, point_visibility, view_visibility  # noqa: F401
+from .horizon import azimuths, grid_horizon, sky_view_factor, point_sky_view, view_sky_view  # noqa: F401
 from .orthophoto import world_pixels, grid_pixels, sample_image, orthophoto, ortho_psnr  # noqa: F401
 from .mosaic import orthomosaic  # noqa: F401
 from .raycast import cast_rays, grid_to_view, surface_priors  # noqa: F401
@@ -35,6 +36,7 @@ __all__ = ["SpSBRDFNeRF", "load_model", "render_rays", "inference", "get_z_vals"
            "register_xy", "apply_registration", "altitude_mae_xy", "fill_holes", "apply_fill",
            "ray_maps", "point_normals", "depth_normals", "view_maps", "OrthoAccumulator", "ortho_image",
            "grid_visibility", "point_visibility", "view_visibility",
+           "azimuths", "grid_horizon", "sky_view_factor", "point_sky_view", "view_sky_view",
            "world_pixels", "grid_pixels", "sample_image", "orthophoto", "ortho_psnr", "orthomosaic",
            "cast_rays", "grid_to_view", "surface_priors",
            "camera", "Rpc", "view_rays", "scene_bounds", "ray_table", "utm_zone", "sun_direction", "depth_priors",

@@ -70,6 +70,7 @@ BN_RPC_NEWTON_ITERS = 8
 BN_CS_ECEF, BN_CS_UTM = 0, 1
 BN_ORTHO_MAX_CHANNELS, BN_ORTHO_EMPTY = 32, -(1 << 63)
 BN_VIS_BLOCKED, BN_VIS_VISIBLE, BN_VIS_NODATA, BN_VIS_MAX_DIRS = 0, 1, 2, 4096
+BN_HORIZON_MAX_DIRS = 4096
 BN_CAST_TOP, BN_CAST_WALL, BN_CAST_MISS, BN_CAST_NODATA, BN_CAST_BELOW, BN_CAST_MAX_SPAN = 0, 1, 2, 3, 4, 65536
 BN_UTM_NEWTON_ITERS, BN_GATHER_MAX_CHANNELS = 4, 32
 BN_GATHER_BILINEAR, BN_GATHER_NEAREST = 0, 1
@@ -201,6 +202,11 @@ _SIGS = {
                                      C.c_double, C.c_double, fptr, fptr, fptr, fptr]),
     "bn_points_visibility": (C.c_int, [fptr, C.c_int64, fptr, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
                                        C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_double, fptr, fptr, fptr, fptr]),
+    "bn_grid_horizon": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32,
+                                  C.c_int32, C.c_double, fptr, fptr, fptr]),
+    "bn_points_horizon": (C.c_int, [fptr, C.c_int64, fptr, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                    C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_double, fptr, fptr, fptr]),
+    "bn_sky_view": (C.c_int, [fptr, C.c_int32, C.c_int64, C.c_int64, C.c_int64, fptr, C.c_int32, fptr, fptr, fptr]),
     "bn_cast_rays": (C.c_int, [fptr, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_double, fptr, C.c_int32, C.c_int32, C.c_double,
                                C.c_double, C.c_double, C.c_double, fptr, fptr, fptr, fptr, fptr, fptr]),
     "bn_utm_geodetic": (C.c_int, [fptr, C.c_int64, C.c_int32, C.c_int32, fptr, fptr, fptr]),

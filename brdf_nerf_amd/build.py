@@ -72,12 +72,14 @@ _TRACKERS = ("-mllvm", "-amdgpu-use-amdgpu-trackers=1") + _NOSLP
 # orthophoto.hip: camera.hip's polynomials (rpc_poly.h) after the inverse UTM, and the bilinear taps, held to a statement bit for bit;
 # mosaic.hip: the same device functions per view (gather_rule.h) and Welford's float64 update, held to a statement bit for bit;
 # raycast.hip: the segment's ends, the crossing parameters (line - u0) / du and z0 + lam dz, held to a statement bit for bit (a
-# contracted multiply-add moves a graze across the <=).
+# contracted multiply-add moves a graze across the <=);
+# horizon.hip: visibility.hip's u0 + t su and v0 + t sv, and the slope (h - z0) / (t L) with its strict s > best, held to a statement
+# bit for bit (a contracted multiply-add moves a step across a cell edge; the sky view's 1 + s s must round the product first).
 FILE_FLAGS = {"field_wgrad.hip": ("-mllvm", "-amdgpu-sched-strategy=max-ilp"), "world.hip": ("-ffp-contract=off",),
               "metrics.hip": ("-ffp-contract=off",), "register.hip": ("-ffp-contract=off",), "view_maps.hip": ("-ffp-contract=off",),
               "camera.hip": ("-ffp-contract=off",), "ortho.hip": ("-ffp-contract=off",), "visibility.hip": ("-ffp-contract=off",),
               "orthophoto.hip": ("-ffp-contract=off",), "mosaic.hip": ("-ffp-contract=off",), "raycast.hip": ("-ffp-contract=off",),
-              "field_fwd.hip": _NOSLP,
+              "horizon.hip": ("-ffp-contract=off",), "field_fwd.hip": _NOSLP,
               "field_bwd.hip": _TRACKERS, "field_adjoint.hip": _TRACKERS, "field_adjbwd.hip": _TRACKERS}
 
 

@@ -27,7 +27,8 @@ BN_SWITCH(BN_NO_FLAT_COMPOSITE)   // A  the per-(sample, channel) scalar composi
 BN_SWITCH(SKINNY_SPLITS)          // A  =<n>: point splits of skinny_wgrad_kernel (default 256)
 BN_SWITCH(BN_W2_BLOCKS)           // A  =<n>: wgrad256, tiles x point splits per round of the 256 CUs (default 256)
 BN_SWITCH(BN_FILL_NO_LDS)         // A  the row pass of the hole filling reads near_row through L2 instead of staging it (profiles/fill_throughput.py)
-BN_SWITCH(BN_DIAG_D8_IN_F32)      // D  the fp32 mode sends its activation derivatives through the 16-bit modes' 8-bit codec (Siren
+BN_SWITCH(BN_HORIZON_NO_ZMAX)     // A  the horizon march without its (zmax - z0) / run <= best exit (profiles/horizon_throughput.py)
+BN_SWITCH(BN_DIAG_D8_IN_F32)     // D  the fp32 mode sends its activation derivatives through the 16-bit modes' 8-bit codec (Siren
                                   //    layers): what the 8-bit D stash alone does to the analytic normals (profiles/diag_c5_rows.py)
 BN_SWITCH(BN_PROBE_NO_A)          // P  chain GEMM without its weight fragment traffic (profiles/probe_gemm_rate.py)
 BN_SWITCH(BN_PROBE_NO_B)          // P  chain GEMM without its LDS fragment traffic

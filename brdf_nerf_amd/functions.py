@@ -1686,3 +1686,108 @@ def cast_rays(rays, center, rng, dsm, xoff, yoff, res, zmax=float("inf"), depth=
                                          (C.c_double * 3)(*center), rng, _p(dsm), H, W, xoff, yoff, res, zmax, _p(depth), _p(state),
                                          _p(cell), _p(nan_cells), _p(counts), _stream()), "bn_cast_rays")
     return depth, state, cell, nan_cells, counts
+
+
+def _horizon_az(name, az):
+    """(D, 2) or (2,) azimuths (east, north) in any float dtype -> (D, 2) float64 on the HOST (the entries check them there), D in
+    [1, BN_HORIZON_MAX_DIRS], every component finite and no row (0, 0), or ValueError by name."""
+    az = torch.as_tensor(az)
+    if not az.is_floating_point():
+        raise ValueError(f"{name}: az are {az.dtype}, not a float dtype")
+    az = az.detach().to(device="cpu", dtype=torch.float64)
+    if az.dim() == 1 and az.numel() == 2:
+        az = az.reshape(1, 2)
+    if az.dim() != 2 or az.shape[1] != 2 or not 1 <= az.shape[0] <= L.BN_HORIZON_MAX_DIRS:
+        raise ValueError(f"{name}: az {tuple(az.shape)} are not (D, 2) or (2,) with D from 1 to {L.BN_HORIZON_MAX_DIRS}")
+    if not bool(torch.isfinite(az).all()) or not bool((az != 0).any(1).all()):
+        raise ValueError(f"{name}: every azimuth must be finite and not (0, 0)")
+    return az.contiguous()
+
+
+def _horizon_scalars(name, res, max_steps, zmax):
+    res, zmax = float(res), float(zmax)
+    max_steps = (1 << 31) - 1 if max_steps is None else min(int(max_steps), (1 << 31) - 1)
+    if not (res > 0 and math.isfinite(res)):
+        raise ValueError(f"{name}: resolution {res} must be positive and finite")
+    if max_steps < 1:
+        raise ValueError(f"{name}: max_steps {max_steps} must be at least 1")
+    if math.isnan(zmax):
+        raise ValueError(f"{name}: zmax is NaN")
+    return res, max_steps, zmax
+
+
+def grid_horizon(dsm, res, az, max_steps=None, zmax=float("inf"), rows=None, slope=None, hit=None, want_hit=False):
+    """The horizon of the cells of a height grid (bn_grid_horizon): dsm (H, W) float32 on the device, az (D, 2) (east, north)
+    horizontal vectors, taken to float64 on the host.  max_steps bounds the march in cells along the dominant axis (None: the
+    grid's longer side).  rows = (row0, row1): only those rows are written (the others are uninitialised unless `slope` / `hit`
+    come in).  slope (D, H, W) float32 and hit (D, H, W) int32 may be given.  -> slope, hit or None (want_hit, or `hit` given)."""
+    name = "grid_horizon"
+    _need(name, dsm, **VIS_DSM)
+    az = _horizon_az(name, az)
+    res, max_steps, zmax = _horizon_scalars(name, res, max_steps, zmax)
+    H, W = dsm.shape
+    D = az.shape[0]
+    row0, row1 = _rows(name, H, rows)
+    slope = _out(name, slope, "slope", F32, (D, H, W), dsm.device, torch.empty)
+    if hit is not None or want_hit:
+        hit = _out(name, hit, "hit", I32, (D, H, W), dsm.device, torch.empty)
+    _on_device(name, dsm, slope, hit)
+    with torch.cuda.device(dsm.device):
+        L.check(L.lib().bn_grid_horizon(_p(dsm), H, W, res, row0, row1, az.numpy().ctypes.data_as(C.POINTER(C.c_double)), D, max_steps,
+                                        zmax, _p(slope), _p(hit), _stream()), "bn_grid_horizon")
+    return slope, hit
+
+
+def points_horizon(points, dsm, xoff, yoff, res, az, max_steps=None, zmax=float("inf"), want_hit=False):
+    """The horizon of world points over a height grid (bn_points_horizon): points (R, 3) float64 (east, north, altitude) on the
+    device (point_cloud's output), dsm (H, W) float32 with its Grid's origin and resolution, az (D, 2).
+    -> slope (D, R) float32, hit (D, R) int32 or None."""
+    name = "points_horizon"
+    points = _need(name, points, **VIS_POINTS)
+    _need(name, dsm, **VIS_DSM)
+    az = _horizon_az(name, az)
+    res, max_steps, zmax = _horizon_scalars(name, res, max_steps, zmax)
+    xoff, yoff = float(xoff), float(yoff)
+    if not (math.isfinite(xoff) and math.isfinite(yoff)):
+        raise ValueError(f"{name}: grid origin ({xoff}, {yoff}) is not finite")
+    _on_device(name, points, dsm)
+    H, W = dsm.shape
+    R, D = points.shape[0], az.shape[0]
+    slope = torch.empty((D, R), dtype=torch.float32, device=dsm.device)
+    hit = torch.empty((D, R), dtype=torch.int32, device=dsm.device) if want_hit else None
+    if R:
+        with torch.cuda.device(dsm.device):
+            L.check(L.lib().bn_points_horizon(_p(points), R, _p(dsm), H, W, xoff, yoff, res, az.numpy().ctypes.data_as(C.POINTER(C.c_double)),
+                                              D, max_steps, zmax, _p(slope), _p(hit), _stream()), "bn_points_horizon")
+    return slope, hit
+
+
+def sky_view(slope, acc, D, cells=None, svf=None, sums=None, last=True):
+    """One tile of the sky-view sum (bn_sky_view): slope (n, ...) float32 planes of the horizon entries, acc float64 with one
+    element per start, zeroed by the caller before the first tile and accumulated into, plane by plane in ascending order; D the
+    TOTAL number of azimuths.  cells = (c0, c1): only those starts (flat indices) are read and written.  last=True (the tile of the
+    last planes): svf (float32, acc's shape) = acc / D and sums (3,) int64 += (sum of llrint(svf 2^30) over the non-NaN ones, their
+    count, the NaN count); svf and sums may be given - sums are accumulated into.  -> acc, svf or None, sums or None."""
+    name = "sky_view"
+    _need(name, slope, "slope", F32, None)
+    _need(name, acc, "acc", F64, None)
+    n_cells = acc.numel()
+    if slope.dim() < 1 or not 1 <= slope.shape[0] <= L.BN_HORIZON_MAX_DIRS or n_cells < 1 or slope.numel() != slope.shape[0] * n_cells:
+        raise ValueError(f"{name}: slope {tuple(slope.shape)} is not 1 to {L.BN_HORIZON_MAX_DIRS} planes of acc's {n_cells} elements")
+    if n_cells > (1 << 30):
+        raise ValueError(f"{name}: acc {tuple(acc.shape)} (1 to 2^30 elements)")
+    D = int(D)
+    if not 1 <= D <= L.BN_HORIZON_MAX_DIRS:
+        raise ValueError(f"{name}: D {D} outside [1, {L.BN_HORIZON_MAX_DIRS}]")
+    c0, c1 = (0, n_cells) if cells is None else (int(cells[0]), int(cells[1]))
+    if not 0 <= c0 <= c1 <= n_cells:
+        raise ValueError(f"{name}: cells ({c0}, {c1}) outside [0, {n_cells}]")
+    if last:
+        svf = _out(name, svf, "svf", F32, tuple(acc.shape), acc.device, torch.empty)
+        sums = _out(name, sums, "sums", I64, (3,), acc.device)
+    elif svf is not None or sums is not None:
+        raise ValueError(f"{name}: svf and sums belong to the last tile (last=True)")
+    _on_device(name, slope, acc, svf, sums)
+    with torch.cuda.device(acc.device):
+        L.check(L.lib().bn_sky_view(_p(slope), slope.shape[0], n_cells, c0, c1, _p(acc), D, _p(svf), _p(sums), _stream()), "bn_sky_view")
+    return acc, svf, sums

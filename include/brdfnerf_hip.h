@@ -1040,6 +1040,66 @@ int bn_points_visibility(const double *enz, int64_t R, const float *dsm, int32_t
 int bn_cast_rays(const float *rays, int64_t ray_stride, int64_t R, const double *center, double range, const float *dsm, int32_t H,
                  int32_t W, double xoff, double yoff, double res, double zmax, float *depth, uint8_t *state, int32_t *cell,
                  int32_t *nan_cells, long long *counts, void *stream);
+/* Horizon and sky view over a surface model (additive to ABI 7): from a start on or above a height grid, march along a horizontal
+ * azimuth and keep the steepest slope met - the tangent of the horizon's elevation - then average cos^2 of that elevation over the
+ * azimuths: the sky-view factor, the geometric counterpart of the `sky` term of the reference's irradiance
+ * sun_v + (1 - sun_v) * sky (models/spsbrdfnerf.py:265-268) as the march of "Visibility over a surface model" is that of sun_v.  The
+ * horizon table answers "is this start shadowed by a sun at elevation e" for every e at once: slope > tan e.  There is NO upstream
+ * counterpart, so the rule is this project's own and there is nothing to check it against but its statement and the shadow march.
+ *
+ * Grid.  dsm float32 [H][W], north-up, NaN = no data, with xoff, yoff, res as in "Visibility over a surface model".
+ * Azimuth.  (dx, dy), float64 (east, north): a horizontal vector, finite, not (0, 0), not necessarily normalised.  az is [D][2] in
+ *   HOST memory: the entries read and check every azimuth before the first launch; the device evaluates no sin or cos.
+ * Everything below is float64 and every operation is rounded on its own (no fused multiply-add).
+ * Start.  Grid mode: cell (j, i) starts at u0 = i + 0.5, v0 = j + 0.5, z0 = (double)dsm[j][i].  Point mode: a point (e, n, a)
+ *   starts at u0 = (e - xoff) / res, v0 = (yoff - n) / res, z0 = a.  A start that is not finite in any coordinate, or a point-mode
+ *   start with !(u0 >= 0 && u0 < W && v0 >= 0 && v0 < H), has no data: slope = NaN, hit = -1.
+ * Step.  a = fmax(fabs(dx), fabs(dy)) ;  su = dx / a ;  sv = -(dy / a) ;  L = sqrt(su * su + sv * sv) * res, the metres of ground
+ *   per step.  One of su, sv is exactly +-1, as in the visibility march.
+ * March.  best = 0.0, hit = -1.  For t = 1 .. min(max(W, H), max_steps):
+ *     tt = (double)t ;  ut = u0 + tt * su ;  vt = v0 + tt * sv                      (the product with t, never a running sum)
+ *     if !(ut >= 0 && ut < W && vt >= 0 && vt < H): stop
+ *     run = tt * L
+ *     if (zmax - z0) / run <= best: stop                                            (the early exit, see below)
+ *     h = (double)dsm[(int)floor(vt)][(int)floor(ut)]
+ *     s = (h - z0) / run
+ *     if s > best: best = s and hit = that cell's flat index floor(vt) W + floor(ut)
+ *   The comparison is strict and false for NaN: the first cell in ascending t wins a tie and a NaN cell never raises the horizon;
+ *   +inf gives best = +inf, -inf never wins.  The start cell itself is never tested.
+ *   slope = (float)best: the tangent of the horizon's elevation, floored at 0 - an open and level horizon beyond the grid's edge.
+ * zmax is an optimisation argument.  If zmax >= every non-NaN cell the early exit cannot change a bit: rounded subtraction is
+ *   monotone, so every later step has fl(h - z0) <= fl(zmax - z0); if fl(zmax - z0) <= 0 every later s <= 0 <= best; otherwise
+ *   rounded division by a growing positive run is monotone too, so every later s is at most the bound just tested, hence at most
+ *   best - and the update needs s strictly greater.  The argument holds at whatever step the test is made, so a kernel may make it
+ *   at some steps only (csrc/horizon.hip tests once per batch of 8 steps, before the batch's loads go out).  zmax = +inf is the
+ *   plain rule (inf / run <= best only once best is +inf, which nothing beats).  A smaller zmax is the caller's error and is not
+ *   detected.
+ * max_steps bounds the march in cells along the dominant axis: a square window around the start, not a disc.
+ * Sky view.  D is the TOTAL number of azimuths; acc float64 [cells] is zeroed by the caller.  Per cell, for k ascending over the n
+ *   planes of the call, one at a time:   s = (double)slope[k][c]   (the STORED float32, not best) ;  acc = acc + 1.0 / (1.0 + s * s)
+ *   and with svf != NULL (the call of the last planes):   v = acc / (double)D ;  svf = (float)v.
+ *   1 / (1 + tan^2) is cos^2 of the horizon's elevation and no transcendental is evaluated; a NaN slope makes svf NaN, an infinite
+ *   one contributes exactly 0.  acc is observable: its bits fix the summation order whatever tiling of the azimuths a caller chooses.
+ *   sums int64 [3] += (the sum of llrint(v 2^30) over the non-NaN v, their count, the NaN count) over [c0, c1): the CALLER zeroes
+ *   them, block-reduced, one integer atomic per counter and block.  There is no float atomic.
+ * Outputs.  slope float32 [D][N], hit int32 [D][N] (nullable), plain stores of the lane's own start: every bit depends on the grid,
+ *   the starts and the azimuths alone - not on blocks, row bands, how D is split over calls, or the number of ranks.
+ * bn_grid_horizon: N = H W, the starts are the cells of rows [row0, row1); only the band's rows are written.  An empty band is
+ *   accepted and launches nothing.
+ * bn_points_horizon: N = R, enz float64 [R][3] = (east, north, altitude) on the device.  R == 0 launches nothing.
+ * bn_sky_view: slope holds n planes of `cells` floats; only cells [c0, c1) of acc and svf are read and written.  An empty range is
+ *   accepted and launches nothing.
+ * Refused (BN_EINVAL, nothing launched, buffers untouched): NULL dsm, az, slope, enz or acc; H or W < 1, or H W > 2^30; D or n outside
+ * [1, BN_HORIZON_MAX_DIRS]; R < 0 or over 2^30; cells outside [1, 2^30]; rows outside [0, H] or row0 > row1; c0, c1 outside [0, cells] or
+ * c0 > c1; res not positive and finite; a non-finite grid origin; max_steps < 1; a NaN zmax; an azimuth with a non-finite component
+ * or both components zero; svf without sums. */
+#define BN_HORIZON_MAX_DIRS 4096
+int bn_grid_horizon(const float *dsm, int32_t H, int32_t W, double res, int32_t row0, int32_t row1, const double *az, int32_t D,
+                    int32_t max_steps, double zmax, float *slope, int32_t *hit, void *stream);
+int bn_points_horizon(const double *enz, int64_t R, const float *dsm, int32_t H, int32_t W, double xoff, double yoff, double res,
+                      const double *az, int32_t D, int32_t max_steps, double zmax, float *slope, int32_t *hit, void *stream);
+int bn_sky_view(const float *slope, int32_t n, int64_t cells, int64_t c0, int64_t c1, double *acc, int32_t D, float *svf,
+                long long *sums, void *stream);
 /* Orthophoto of an observed image (additive to ABI 7): every cell of a surface model is taken to the pixel of a satellite image
  * that saw it, and the image - or any per-pixel raster in image geometry - is gathered there.  The ortho entries above splat a
  * VIEW's rays into cells; this is the opposite direction.  There is NO upstream counterpart - the reference never orthorectifies
