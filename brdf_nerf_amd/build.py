@@ -71,6 +71,8 @@ _TRACKERS = ("-mllvm", "-amdgpu-use-amdgpu-trackers=1") + _NOSLP
 # visibility.hip: the march's u0 + t su, v0 + t sv, z0 + t sz and zt + eps (a contracted multiply-add moves a step across a cell edge);
 # orthophoto.hip: camera.hip's polynomials (rpc_poly.h) after the inverse UTM, and the bilinear taps, held to a statement bit for bit;
 # mosaic.hip: the same device functions per view (gather_rule.h) and Welford's float64 update, held to a statement bit for bit;
+# sweep.hip: mosaic.hip's per-view step (view_step.h) per altitude level, a0 + off[l] and the sum of M2 / n over the channels with its
+# strict v < best, held to a statement bit for bit (a contracted multiply-add in Welford's update moves a tie between two levels);
 # raycast.hip: the segment's ends, the crossing parameters (line - u0) / du and z0 + lam dz, held to a statement bit for bit (a
 # contracted multiply-add moves a graze across the <=);
 # horizon.hip: visibility.hip's u0 + t su and v0 + t sv, and the slope (h - z0) / (t L) with its strict s > best, held to a statement
@@ -79,7 +81,7 @@ FILE_FLAGS = {"field_wgrad.hip": ("-mllvm", "-amdgpu-sched-strategy=max-ilp"), "
               "metrics.hip": ("-ffp-contract=off",), "register.hip": ("-ffp-contract=off",), "view_maps.hip": ("-ffp-contract=off",),
               "camera.hip": ("-ffp-contract=off",), "ortho.hip": ("-ffp-contract=off",), "visibility.hip": ("-ffp-contract=off",),
               "orthophoto.hip": ("-ffp-contract=off",), "mosaic.hip": ("-ffp-contract=off",), "raycast.hip": ("-ffp-contract=off",),
-              "horizon.hip": ("-ffp-contract=off",), "field_fwd.hip": _NOSLP,
+              "horizon.hip": ("-ffp-contract=off",), "sweep.hip": ("-ffp-contract=off",), "field_fwd.hip": _NOSLP,
               "field_bwd.hip": _TRACKERS, "field_adjoint.hip": _TRACKERS, "field_adjbwd.hip": _TRACKERS}
 
 

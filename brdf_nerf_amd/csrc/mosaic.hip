@@ -8,7 +8,8 @@
 //                           them, geodesy.h's utm_geodetic ONCE, then for k = 0 .. K - 1: rpc_poly.h's project under view k's
 //                           descriptor (or the pixel read from colrow_in), gather_rule.h's state and value - bn_grid_pixels' and
 //                           bn_image_gather's device functions on the same operands, so a view's value is the K-launch chain's
-//                           bits - and Welford's update of the C means and sums of squares in float64.
+//                           bits - and Welford's update of the C means and sums of squares in float64.  That per-view step is
+//                           view_step.h's add_view, which sweep.hip walks per altitude level.
 //
 // The K view records (776 bytes each) live in device memory and are read with the loop's own index, which every lane shares: the
 // compiler fetches them through the scalar cache, as kernel arguments are fetched.  C is a template parameter and every per-channel
@@ -23,6 +24,7 @@
 #include "gather_rule.h"
 #include "geodesy.h"
 #include "rpc_poly.h"
+#include "view_step.h"
 // every float64 operation below is rounded on its own (see above); the build also passes -ffp-contract=off for this file
 #pragma clang fp contract(off)
 
@@ -31,7 +33,6 @@ namespace {
 using namespace geodesy;
 
 constexpr int MOS_BLOCK = 256;
-constexpr int64_t MOS_MAX_CELLS = (int64_t)1 << 30;
 constexpr uint32_t F32_NAN_BITS = 0x7FC00000u;
 constexpr double Q20 = 1048576.0;
 
@@ -80,45 +81,14 @@ void grid_mosaic_kernel(const MosaicArgs A) {
     const bn_mosaic_view &V = A.views[k];                            // k is the same in every lane: scalar loads
     int st = -1;                                                     // a lane outside the band counts nowhere
     if (live) {
-      double col, row;
-      if (A.colrow_in) {
-        const double *cr = A.colrow_in + 2 * ((int64_t)k * A.HW + c);
-        col = cr[0];
-        row = cr[1];
-      } else {
-        rpc_poly::project(V.rpc, lon, lat, a, col, row);
-        if (bad0 || !(isfinite(a) && isfinite(col) && isfinite(row))) col = row = __builtin_nan("");
-      }
-      st = gather_rule::cell_state(col, row, V.Hi, V.Wi, V.vis, c);
-      if (st == BN_GATHER_KEPT) {
-        uint32_t v[C];
-        if (A.mode == BN_GATHER_NEAREST) {
-          const uint32_t *src = reinterpret_cast<const uint32_t *>(V.img) + gather_rule::nearest_at(col, row, V.Hi, V.Wi, V.s_row, V.s_col);
+      uint32_t v[C];
+      st = view_step::add_view<C>(V, A.colrow_in ? A.colrow_in + 2 * ((int64_t)k * A.HW + c) : nullptr, c, bad0, lon, lat, a, A.mode, n,
+                                  m, M2, v);
+      if (st == BN_MOSAIC_USED && (n == 1 || V.rank < best_rank)) {
+        best = k;
+        best_rank = V.rank;
 #pragma unroll
-          for (int ch = 0; ch < C; ++ch) v[ch] = src[ch * V.s_chan];                       // the pixel's 32 bits
-        } else {
-          const gather_rule::Taps4 t = gather_rule::bilinear_taps(col, row, V.Hi, V.Wi, V.s_row, V.s_col);
-#pragma unroll
-          for (int ch = 0; ch < C; ++ch) v[ch] = __float_as_uint(gather_rule::bilinear(V.img + ch * V.s_chan, t));
-        }
-        bool finite = true;
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) finite = finite && isfinite(__uint_as_float(v[ch]));
-        if (!finite) {
-          st = BN_MOSAIC_NONFINITE;
-        } else {
-          n = n + 1;
-          const bool wins = n == 1 || V.rank < best_rank;
-          if (wins) { best = k; best_rank = V.rank; }
-#pragma unroll
-          for (int ch = 0; ch < C; ++ch) {
-            const double x = (double)__uint_as_float(v[ch]);
-            const double delta = x - m[ch];
-            m[ch] = m[ch] + delta / (double)n;
-            M2[ch] = M2[ch] + delta * (x - m[ch]);
-            if (wins) bv[ch] = v[ch];
-          }
-        }
+        for (int ch = 0; ch < C; ++ch) bv[ch] = v[ch];
       }
     }
 #pragma unroll
@@ -167,24 +137,7 @@ extern "C" int bn_grid_mosaic(const bn_mosaic_view *views_host, const bn_mosaic_
                               int32_t *best, float *best_val, float *mean, float *std, unsigned long long *counts,
                               unsigned long long *sums, void *stream) {
   BN_REQUIRE(views_host && views_dev && dsm && count && counts, "grid_mosaic: null argument");
-  BN_REQUIRE(K >= 1 && K <= BN_MOSAIC_MAX_VIEWS, "grid_mosaic: K=%d views outside [1, %d]", K, BN_MOSAIC_MAX_VIEWS);
-  BN_REQUIRE(C >= 1 && C <= BN_MOSAIC_MAX_CHANNELS, "grid_mosaic: C=%d channels outside [1, %d]", C, BN_MOSAIC_MAX_CHANNELS);
-  BN_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= MOS_MAX_CELLS, "grid_mosaic: grid %d x %d (H W from 1 to 2^30 cells)", H, W);
-  BN_REQUIRE(0 <= row0 && row0 <= row1 && row1 <= H, "grid_mosaic: rows [%d, %d) outside [0, %d)", row0, row1, H);
-  BN_REQUIRE(res > 0.0 && std::isfinite(res), "grid_mosaic: resolution %g must be positive and finite", res);
-  BN_REQUIRE(std::isfinite(xoff) && std::isfinite(yoff), "grid_mosaic: grid origin (%g, %g) is not finite", xoff, yoff);
-  BN_REQUIRE(zone >= 1 && zone <= 60, "grid_mosaic: zone=%d outside [1, 60]", zone);
-  BN_REQUIRE(south == 0 || south == 1, "grid_mosaic: south=%d (0 or 1)", south);
-  BN_REQUIRE(mode == BN_GATHER_BILINEAR || mode == BN_GATHER_NEAREST, "grid_mosaic: mode=%d (BN_GATHER_BILINEAR or BN_GATHER_NEAREST)",
-             mode);
-  for (int32_t k = 0; k < K; ++k) {
-    const bn_mosaic_view &v = views_host[k];
-    BN_REQUIRE(v.img, "grid_mosaic: view %d has no image", k);
-    BN_REQUIRE(v.Hi >= 1 && v.Wi >= 1, "grid_mosaic: view %d has an image of %d x %d pixels", k, v.Hi, v.Wi);
-    BN_REQUIRE(v.s_row >= 0 && v.s_col >= 0 && v.s_chan >= 0, "grid_mosaic: view %d has a negative stride (%lld, %lld, %lld)", k,
-               (long long)v.s_row, (long long)v.s_col, (long long)v.s_chan);
-    BN_REQUIRE(rpc_poly::rpc_ok(&v.rpc), "grid_mosaic: the descriptor of view %d has a zero scale or a non-finite entry", k);
-  }
+  if (view_step::check_views_on_grid("grid_mosaic", views_host, K, C, H, W, xoff, yoff, res, row0, row1, zone, south, mode)) return BN_EINVAL;
   if (row0 == row1) return 0;
   MosaicArgs a;
   a.views = views_dev; a.dsm = dsm; a.colrow_in = colrow_in;

@@ -5,6 +5,7 @@ every numerical step of the hot path runs in the HIP library.  No CPU fallback e
 """
 import ctypes as C
 import math
+import numbers
 import os
 
 import torch
@@ -1583,6 +1584,34 @@ def grid_mosaic(views, C_, dsm, xoff, yoff, res, zone, south, rows=None, mode="b
     counts and sums are accumulated into; a map that is neither given nor named in `want` is not computed (None).
     -> {"count", "best", "best_val", "mean", "std", "counts", "sums"}."""
     name = "grid_mosaic"
+    K, C_, zone, south, (xoff, yoff, res), (H, W), (row0, row1), specs, held = _views_on_grid(name, views, C_, dsm, xoff, yoff, res, zone,
+                                                                                          south, rows, mode)
+    _maybe(name, colrow, "colrow", F64, (K, H, W, 2))
+    dev = dsm.device
+    wanted = lambda t, key: t is not None or key in want
+    count = _out(name, count, "count", U8, (H, W), dev, torch.empty)
+    best = _out(name, best, "best", I32, (H, W), dev, torch.empty) if wanted(best, "best") else None
+    best_val = _out(name, best_val, "best_val", F32, (C_, H, W), dev, torch.empty) if wanted(best_val, "best_val") else None
+    mean = _out(name, mean, "mean", F32, (C_, H, W), dev, torch.empty) if wanted(mean, "mean") else None
+    std = _out(name, std, "std", F32, (C_, H, W), dev, torch.empty) if wanted(std, "std") else None
+    counts = _out(name, counts, "counts", I64, (K, 5), dev)
+    sums = _out(name, sums, "sums", I64, (3,), dev, flat=True)
+    _on_device(name, dsm, colrow, count, best, best_val, mean, std, counts, sums, *held)
+    table = _view_table(specs)
+    with torch.cuda.device(dev):
+        # the same bytes on the device, which the kernel reads; the library checks the host copy and copies nothing.  The copy and
+        # the launch are on one stream, so the buffer may go back to the allocator when this call returns
+        table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=U8).to(dev)
+        L.check(L.lib().bn_grid_mosaic(table, _p(table_dev), K, C_, _p(dsm), H, W, xoff, yoff, res, row0, row1, zone, south,
+                                       GATHER_MODES[mode], _p(colrow), _p(count), _p(best), _p(best_val), _p(mean), _p(std),
+                                       _p(counts), _p(sums), _stream()), "bn_grid_mosaic")
+    return {"count": count, "best": best, "best_val": best_val, "mean": mean, "std": std, "counts": counts, "sums": sums}
+
+
+def _views_on_grid(name, views, C_, dsm, xoff, yoff, res, zone, south, rows, mode):
+    """The host-side checks grid_mosaic and grid_sweep share: K views of C_ channels over the grid of `dsm`, each (img, Hi, Wi,
+    strides, vis, rank, rpc) -> K, C_, zone, south, (xoff, yoff, res), (H, W), (row0, row1), the views' records for _view_table and
+    the tensors they hold (for _on_device), or ValueError by `name`."""
     views = list(views)
     K, C_ = len(views), int(C_)
     if not 1 <= K <= L.BN_MOSAIC_MAX_VIEWS:
@@ -1612,30 +1641,78 @@ def grid_mosaic(views, C_, dsm, xoff, yoff, res, zone, south, rows=None, mode="b
             raise ValueError(f"{name}: rank {rank!r} of view {k} is not a 32-bit integer")
         held += [img, vis]
         specs.append((img, vis, Hi, Wi, sr, sc, sp, int(rank), rpc.struct))
-    _maybe(name, colrow, "colrow", F64, (K, H, W, 2))
-    dev = dsm.device
-    wanted = lambda t, key: t is not None or key in want
-    count = _out(name, count, "count", U8, (H, W), dev, torch.empty)
-    best = _out(name, best, "best", I32, (H, W), dev, torch.empty) if wanted(best, "best") else None
-    best_val = _out(name, best_val, "best_val", F32, (C_, H, W), dev, torch.empty) if wanted(best_val, "best_val") else None
-    mean = _out(name, mean, "mean", F32, (C_, H, W), dev, torch.empty) if wanted(mean, "mean") else None
-    std = _out(name, std, "std", F32, (C_, H, W), dev, torch.empty) if wanted(std, "std") else None
-    counts = _out(name, counts, "counts", I64, (K, 5), dev)
-    sums = _out(name, sums, "sums", I64, (3,), dev, flat=True)
-    _on_device(name, dsm, colrow, count, best, best_val, mean, std, counts, sums, *held)
-    table = (L.MosaicView * K)()
+    return K, C_, zone, south, (xoff, yoff, res), (H, W), (row0, row1), specs, held
+
+
+def _view_table(specs):
+    """_views_on_grid's records as the bn_mosaic_view table in host memory."""
+    table = (L.MosaicView * len(specs))()
     for v, (img, vis, *scalars, rpc) in zip(table, specs):
         v.img, v.vis = img.data_ptr(), None if vis is None else vis.data_ptr()
         v.Hi, v.Wi, v.s_row, v.s_col, v.s_chan, v.rank = scalars
         v.rpc = rpc
+    return table
+
+
+def _sweep_offsets(name, offsets):
+    """Z offsets in metres, a sequence or a tensor of any real dtype -> (Z,) float64 on the HOST (the entry checks them there), Z in
+    [1, BN_SWEEP_MAX_LEVELS], every one finite, or ValueError by name."""
+    try:
+        off = torch.as_tensor(offsets).detach().to(device="cpu", dtype=torch.float64)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{name}: offsets {offsets!r} are not a sequence of numbers") from None
+    if off.dim() != 1 or not 1 <= off.numel() <= L.BN_SWEEP_MAX_LEVELS:
+        raise ValueError(f"{name}: offsets {tuple(off.shape)} are not 1 to {L.BN_SWEEP_MAX_LEVELS} levels")
+    if not bool(torch.isfinite(off).all()):
+        raise ValueError(f"{name}: every offset must be finite")
+    return off.contiguous()
+
+
+def _sweep_min_views(name, min_views):
+    """The views a level needs to be valid: an integer (not a bool) from 1 to BN_MOSAIC_MAX_VIEWS -> int, or ValueError by name."""
+    if isinstance(min_views, bool) or not isinstance(min_views, numbers.Integral) or not 1 <= min_views <= L.BN_MOSAIC_MAX_VIEWS:
+        raise ValueError(f"{name}: min_views {min_views!r} is not an integer from 1 to {L.BN_MOSAIC_MAX_VIEWS}")
+    return int(min_views)
+
+
+def grid_sweep(views, C_, dsm, xoff, yoff, res, zone, south, offsets, min_views=2, rows=None, mode="bilinear", colrow=None, level=None,
+               cost_min=None, count=None, altitude=None, cost=None, valid=None, wins=None, sums=None, want_cost=False):
+    """The altitude sweep of a height grid under K images in one launch (bn_grid_sweep).  views, C_, dsm, xoff, yoff, res, zone, south,
+    rows, mode: as grid_mosaic takes them (a view's rank is not read).  offsets: Z floats in metres, 1 to 256, any order; min_views:
+    a level needs that many views to be valid.  colrow (Z, K, H, W, 2) float64 or None: the pixels per level and view, used in place
+    of the projection.  level (H, W) int32, cost_min and altitude (H, W) float32, count (H, W) uint8, cost (Z, H, W) float32 (made only
+    with want_cost, or given), valid and wins (Z,) int64 and sums (3,) int64 = (cells, q, skipped) may be given - the counters are
+    accumulated into.  -> {"level", "cost_min", "count", "altitude", "cost" or None, "valid", "wins", "sums", "offsets" (Z,) float64 on
+    the host}."""
+    name = "grid_sweep"
+    K, C_, zone, south, (xoff, yoff, res), (H, W), (row0, row1), specs, held = _views_on_grid(name, views, C_, dsm, xoff, yoff, res, zone,
+                                                                                          south, rows, mode)
+    off = _sweep_offsets(name, offsets)
+    Z = off.numel()
+    min_views = _sweep_min_views(name, min_views)
+    _maybe(name, colrow, "colrow", F64, (Z, K, H, W, 2))
+    dev = dsm.device
+    level = _out(name, level, "level", I32, (H, W), dev, torch.empty)
+    cost_min = _out(name, cost_min, "cost_min", F32, (H, W), dev, torch.empty)
+    count = _out(name, count, "count", U8, (H, W), dev, torch.empty)
+    altitude = _out(name, altitude, "altitude", F32, (H, W), dev, torch.empty)
+    if cost is not None or want_cost:
+        cost = _out(name, cost, "cost", F32, (Z, H, W), dev, torch.empty)
+    valid = _out(name, valid, "valid", I64, (Z,), dev, flat=True)
+    wins = _out(name, wins, "wins", I64, (Z,), dev, flat=True)
+    sums = _out(name, sums, "sums", I64, (3,), dev, flat=True)
+    _on_device(name, dsm, colrow, level, cost_min, count, altitude, cost, valid, wins, sums, *held)
+    table = _view_table(specs)
     with torch.cuda.device(dev):
-        # the same bytes on the device, which the kernel reads; the library checks the host copy and copies nothing.  The copy and
-        # the launch are on one stream, so the buffer may go back to the allocator when this call returns
+        # the table and the offsets twice, as grid_mosaic passes its table: the library checks the host copies and copies nothing
         table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=U8).to(dev)
-        L.check(L.lib().bn_grid_mosaic(table, _p(table_dev), K, C_, _p(dsm), H, W, xoff, yoff, res, row0, row1, zone, south,
-                                       GATHER_MODES[mode], _p(colrow), _p(count), _p(best), _p(best_val), _p(mean), _p(std),
-                                       _p(counts), _p(sums), _stream()), "bn_grid_mosaic")
-    return {"count": count, "best": best, "best_val": best_val, "mean": mean, "std": std, "counts": counts, "sums": sums}
+        off_dev = off.to(dev)
+        L.check(L.lib().bn_grid_sweep(table, _p(table_dev), K, C_, _p(dsm), H, W, xoff, yoff, res, row0, row1, zone, south,
+                                      GATHER_MODES[mode], off.numpy().ctypes.data_as(C.POINTER(C.c_double)), _p(off_dev), Z, min_views,
+                                      _p(colrow), _p(level), _p(cost_min), _p(count), _p(altitude), _p(cost), _p(valid), _p(wins),
+                                      _p(sums), _stream()), "bn_grid_sweep")
+    return {"level": level, "cost_min": cost_min, "count": count, "altitude": altitude, "cost": cost, "valid": valid, "wins": wins,
+            "sums": sums, "offsets": off}
 
 
 def _cast_scalars(name, center, rng, xoff, yoff, res, zmax):

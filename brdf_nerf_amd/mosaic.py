@@ -55,20 +55,9 @@ def nadir_ranks(view_dirs):
     return rank
 
 
-@torch.no_grad()
-def orthomosaic(views, dsm, grid, zone, south=False, occlusion=True, eps=0.0, view_dirs=None, alt_bounds=None, rank=None,
-                mode="bilinear", rows=None, group=None, layout="image", colrow=None):
-    """Several observed images fused on the grid of a DSM.  views: a list of K (image, H_img, W_img, rpc), each as orthophoto takes
-    one, all of the same 1 to 4 channels, K from 1 to 32; dsm, grid, zone, south, eps, mode, layout, rows, group: as orthophoto.
-    occlusion=True: ONE grid_visibility(dsm, grid.resolution, view_dirs (K, 3), eps) decides which cells each sensor saw; view_dirs
-    are given or camera.view_direction of every view between alt_bounds (orthophoto's default).  rank: K integers, the smaller
-    wins `best`; by default nadir_ranks(view_dirs), and the views' order without occlusion and without view_dirs.  colrow (K, H, W,
-    2) float64: the views' pixels as grid_pixels gives them, used in place of the projection.
-    -> {"best_rgb", "mean", "std" (C, H, W) float32, NaN where no view saw the cell, "count" (H, W) uint8, "best" (H, W) int32 (-1
-    there), "visible" (K, H, W) uint8 as grid_visibility's (None without occlusion), "view_dirs" float64 (K, 3) on the host or None,
-    "rank" [K ints], "counts" {"nodata", "outside", "occluded", "used", "nonfinite": [K ints]}, "consistency": q / (cells C 2^20),
-    NaN without a cell seen twice, "cells", "skipped"}."""
-    name = "orthomosaic"
+def views_on_dsm(name, views, dsm, grid, zone, south, eps, mode, rows, group, layout):
+    """What orthomosaic and sweep.altitude_sweep check of their views, the DSM, the zone, the mode, the layout and the rows, in one
+    place -> the views as (image, H_img, W_img, strides, rpc, C) each, K, C, zone, south, the GridWalk of the rows, res, eps."""
     views = list(views)
     K = len(views)
     if not 1 <= K <= L.BN_MOSAIC_MAX_VIEWS:
@@ -87,9 +76,35 @@ def orthomosaic(views, dsm, grid, zone, south=False, occlusion=True, eps=0.0, vi
     if mode not in Fn.GATHER_MODES:
         raise ValueError(f"{name}: mode {mode!r} ('bilinear' or 'nearest')")
     zone, south = Fn._zone(name, zone, south)
-    H, W = dsm.shape
-    walk = GridWalk(name, H, rows, group)
+    walk = GridWalk(name, dsm.shape[0], rows, group)
     res, eps, _ = Fn._vis_scalars(name, grid.resolution, eps, 0.0)
+    return taken, K, C, zone, south, walk, res, eps
+
+
+def sensor_masks(walk, dsm, res, view_dirs, eps, counts):
+    """The ONE grid_visibility launch towards the K sensors over the walk's rows -> visible (K, H, W) uint8, NODATA in the unseen
+    rows of a lone band; counts (K, 3) int64 are accumulated into."""
+    K, (H, W) = len(view_dirs), dsm.shape
+    return Fn.grid_visibility(dsm, res, view_dirs, eps, _zmax(dsm), rows=walk.rows, counts=counts,
+                              vis=walk.buffer((K, H, W), Fn.U8, VIS_NODATA, dsm.device))[0]
+
+
+@torch.no_grad()
+def orthomosaic(views, dsm, grid, zone, south=False, occlusion=True, eps=0.0, view_dirs=None, alt_bounds=None, rank=None,
+                mode="bilinear", rows=None, group=None, layout="image", colrow=None):
+    """Several observed images fused on the grid of a DSM.  views: a list of K (image, H_img, W_img, rpc), each as orthophoto takes
+    one, all of the same 1 to 4 channels, K from 1 to 32; dsm, grid, zone, south, eps, mode, layout, rows, group: as orthophoto.
+    occlusion=True: ONE grid_visibility(dsm, grid.resolution, view_dirs (K, 3), eps) decides which cells each sensor saw; view_dirs
+    are given or camera.view_direction of every view between alt_bounds (orthophoto's default).  rank: K integers, the smaller
+    wins `best`; by default nadir_ranks(view_dirs), and the views' order without occlusion and without view_dirs.  colrow (K, H, W,
+    2) float64: the views' pixels as grid_pixels gives them, used in place of the projection.
+    -> {"best_rgb", "mean", "std" (C, H, W) float32, NaN where no view saw the cell, "count" (H, W) uint8, "best" (H, W) int32 (-1
+    there), "visible" (K, H, W) uint8 as grid_visibility's (None without occlusion), "view_dirs" float64 (K, 3) on the host or None,
+    "rank" [K ints], "counts" {"nodata", "outside", "occluded", "used", "nonfinite": [K ints]}, "consistency": q / (cells C 2^20),
+    NaN without a cell seen twice, "cells", "skipped"}."""
+    name = "orthomosaic"
+    taken, K, C, zone, south, walk, res, eps = views_on_dsm(name, views, dsm, grid, zone, south, eps, mode, rows, group, layout)
+    H, W = dsm.shape
     if rank is not None:
         rank = list(rank)
         if len(rank) != K or any(isinstance(r, bool) or not isinstance(r, numbers.Integral) or not -(1 << 31) <= r < 1 << 31 for r in rank):
@@ -105,8 +120,7 @@ def orthomosaic(views, dsm, grid, zone, south=False, occlusion=True, eps=0.0, vi
     counts, sums = totals[:5 * K].view(K, 5), totals[5 * K:5 * K + 3]
     visible = None
     if occlusion:
-        visible, _, _ = Fn.grid_visibility(dsm, res, view_dirs, eps, _zmax(dsm), rows=walk.rows, counts=totals[5 * K + 3:].view(K, 3),
-                                           vis=walk.buffer((K, H, W), Fn.U8, VIS_NODATA, dev))
+        visible = sensor_masks(walk, dsm, res, view_dirs, eps, totals[5 * K + 3:].view(K, 3))
     table = [(t[0], t[1], t[2], t[3], None if visible is None else visible[k], rank[k], t[4]) for k, t in enumerate(taken)]
     out = Fn.grid_mosaic(table, C, dsm, grid.xoff, grid.yoff, res, zone, south, rows=walk.rows, mode=mode, colrow=colrow,
                          count=walk.buffer((H, W), Fn.U8, 0, dev), best=walk.buffer((H, W), Fn.I32, -1, dev),

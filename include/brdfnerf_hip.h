@@ -1234,6 +1234,58 @@ int bn_grid_mosaic(const bn_mosaic_view *views_host, const bn_mosaic_view *views
                    int32_t H, int32_t W, double xoff, double yoff, double res, int32_t row0, int32_t row1, int32_t zone,
                    int32_t south, int32_t mode, const double *colrow_in, uint8_t *count, int32_t *best, float *best_val, float *mean,
                    float *std, unsigned long long *counts, unsigned long long *sums, void *stream);
+/* Altitude sweep of a surface model under several observed images (additive to ABI 7): the orthomosaic's spread says THAT a surface
+ * model is wrong - a wrong altitude sends a cell to different ground in every image - but not by how much nor in which direction.
+ * One launch evaluates the spread with the cell's altitude moved through a list of Z offsets and keeps the offset at which it is
+ * smallest: a plane sweep around the surface model.  It gives a per-cell altitude residual, a refined model (dsm + best offset) and,
+ * from a constant dsm with offsets that span the scene, a surface model from the images alone; none needs ground truth.  There is NO
+ * upstream counterpart.  Float64, every operation rounded on its own (csrc/sweep.hip is compiled with fp contraction off).
+ *
+ * views_host / views_dev, K, C, dsm, H, W, xoff, yoff, res, row0, row1, zone, south, mode: as bn_grid_mosaic takes them (rank is not
+ *   read).  offsets_host / offsets_dev: the same Z float64 offsets in metres in host memory - checked before the launch - and in
+ *   device memory, which the kernel reads; Z in [1, BN_SWEEP_MAX_LEVELS]; they need not be sorted or distinct.  min_views in [1,
+ *   BN_MOSAIC_MAX_VIEWS].  colrow_in (nullable): float64 [Z][K][H][W][2] = (col, row) per level, view and cell, on the device; when
+ *   given, the inverse UTM and the projections are skipped and these pixels are used.
+ *
+ * Per cell c = (j, i) of rows [row0, row1):
+ * 1. centre     e, nn and a0 = (double)dsm[c] as step 1 of "Orthophoto of an observed image"; bad0 and (lon, lat) as step 2 of
+ *               "Orthomosaic of several observed images" - the inverse UTM runs ONCE per cell, not per level or view.
+ * 2. levels     best_level = -1 ; then for l = 0 .. Z - 1, ascending:
+ *               a_l = a0 + off[l]                                      (one float64 addition; never formed in float32)
+ *               n = 0 ; m_c = 0.0, M2_c = 0.0 for c < C ; then for k = 0 .. K - 1, ascending, steps 3 a - e of the orthomosaic on (lon,
+ *               lat, a_l): the pixel under rpc_k, NaN in both if bad0 || !(isfinite(a_l) && isfinite(col) && isfinite(row)) (with
+ *               colrow_in: colrow_in[l][k][c]); the state with Hi_k, Wi_k and vis_k - the mask is the base model's and the same at
+ *               every level; for a kept cell its C values in `mode`; a view with a NaN or infinite value contributes nothing;
+ *               otherwise n = n + 1 and per channel x = (double)v_c ; delta = x - m_c ; m_c = m_c + delta / (double)n ; M2_c = M2_c +
+ *               delta * (x - m_c).  (One device function, csrc/view_step.h, under both kernels.)
+ * 3. cost       level l is valid iff n >= min_views.  v_l = 0.0 ; for c ascending: v_l = v_l + M2_c / (double)n - the sum of the
+ *               channels' population variances, NOT the square of a rounded square root.
+ * 4. volume     if cost != NULL: cost[l][c] = (float)v_l when the level is valid, else NaN.
+ * 5. argmin     if the level is valid and (best_level < 0 || v_l < best_v): best_level = l, best_v = v_l, best_n = n.  The
+ *               comparison is strict: the FIRST level in ascending l keeps a tie.
+ * Outputs, each a plain store of the lane's own cell, only the band's rows written; best_cost, best_count, altitude and cost are
+ * nullable one by one:
+ *   best_level  int32 [H][W]      -1 when no level is valid
+ *   best_cost   float32 [H][W]    (float)best_v ; NaN when none
+ *   best_count  uint8 [H][W]      best_n ; 0 when none
+ *   altitude    float32 [H][W]    (float)(a0 + off[best_level]) ; NaN when none
+ *   cost        float32 [Z][H][W] step 4
+ *   valid       uint64 [Z]        += the cells of the band that are valid at level l
+ *   wins        uint64 [Z]        += the cells of the band whose best is level l
+ *   sums        uint64 [3]        += (cells, q, skipped) over the cells with a best: cells += 1; q += llrint(best_v 2^20) if best_v <
+ *                                 2^20, otherwise skipped += 1.  The mean cost of the grid is q / (cells 2^20).
+ * valid, wins and sums are device memory, the CALLER zeroes them; at most 2 Z + 3 integer atomics per block; there is no float
+ * atomic.  Every bit depends on the inputs alone - not on blocks, row bands or the number of ranks (the bands are gathered, the
+ * counters add up).  An empty band is accepted and launches nothing.
+ * Refused (BN_EINVAL, nothing launched, buffers untouched): everything bn_grid_mosaic refuses of the views, K, C, the grid, the rows,
+ * the zone and the mode; NULL views_host, views_dev, dsm, offsets_host, offsets_dev, best_level, valid, wins or sums; Z outside [1,
+ * BN_SWEEP_MAX_LEVELS]; an offset that is not finite; min_views outside [1, BN_MOSAIC_MAX_VIEWS]. */
+#define BN_SWEEP_MAX_LEVELS 256
+int bn_grid_sweep(const bn_mosaic_view *views_host, const bn_mosaic_view *views_dev, int32_t K, int32_t C, const float *dsm,
+                  int32_t H, int32_t W, double xoff, double yoff, double res, int32_t row0, int32_t row1, int32_t zone,
+                  int32_t south, int32_t mode, const double *offsets_host, const double *offsets_dev, int32_t Z, int32_t min_views,
+                  const double *colrow_in, int32_t *best_level, float *best_cost, uint8_t *best_count, float *altitude, float *cost,
+                  unsigned long long *valid, unsigned long long *wins, unsigned long long *sums, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
