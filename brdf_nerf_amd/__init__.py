@@ -23,6 +23,7 @@ from .horizon import azimuths, grid_horizon, sky_view_factor, point_sky_view, vi
 from .orthophoto import world_pixels, grid_pixels, sample_image, orthophoto, ortho_psnr  # noqa: F401
 from .mosaic import orthomosaic  # noqa: F401
 from .sweep import altitude_sweep  # noqa: F401
+from .aggregate import aggregate_costs  # noqa: F401
 from .raycast import cast_rays, grid_to_view, surface_priors  # noqa: F401
 from . import camera  # noqa: F401
 from .camera import Rpc, view_rays, scene_bounds, ray_table, utm_zone, sun_direction, depth_priors, nearest_lines  # noqa: F401
@@ -39,7 +40,7 @@ __all__ = ["SpSBRDFNeRF", "load_model", "render_rays", "inference", "get_z_vals"
            "grid_visibility", "point_visibility", "view_visibility",
            "azimuths", "grid_horizon", "sky_view_factor", "point_sky_view", "view_sky_view",
            "world_pixels", "grid_pixels", "sample_image", "orthophoto", "ortho_psnr", "orthomosaic",
-           "altitude_sweep",
+           "altitude_sweep", "aggregate_costs",
            "cast_rays", "grid_to_view", "surface_priors",
            "camera", "Rpc", "view_rays", "scene_bounds", "ray_table", "utm_zone", "sun_direction", "depth_priors",
            "nearest_lines", "ecef_geodetic"]

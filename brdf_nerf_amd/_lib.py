@@ -77,6 +77,7 @@ BN_GATHER_BILINEAR, BN_GATHER_NEAREST = 0, 1
 BN_GATHER_NODATA, BN_GATHER_OUTSIDE, BN_GATHER_OCCLUDED, BN_GATHER_KEPT = 0, 1, 2, 3
 BN_MOSAIC_MAX_VIEWS, BN_MOSAIC_MAX_CHANNELS, BN_MOSAIC_USED, BN_MOSAIC_NONFINITE = 32, 4, 3, 4
 BN_SWEEP_MAX_LEVELS = 256
+BN_AGG_QINV = 1 << 20
 
 
 class Rpc(C.Structure):               # bn_rpc: 90 doubles
@@ -221,6 +222,9 @@ _SIGS = {
     "bn_grid_sweep": (C.c_int, [C.POINTER(MosaicView), fptr, C.c_int32, C.c_int32, fptr, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                 C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), fptr, C.c_int32,
                                 C.c_int32, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr, fptr]),
+    "bn_cost_quanta": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_int32, C.c_double, fptr, fptr, fptr]),
+    "bn_cost_paths": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fptr, fptr]),
+    "bn_cost_pick": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, C.c_int32, fptr, fptr, fptr, fptr, fptr]),
     "bn_ssim_map": (C.c_int, [fptr, fptr, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, fptr, C.c_double,
                               C.c_double, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32, fptr, fptr, fptr]),
     "bn_grid_normals": (C.c_int, [fptr, C.c_int32, C.c_int32, C.c_double, fptr, fptr]),

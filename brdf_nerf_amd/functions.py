@@ -1715,6 +1715,80 @@ def grid_sweep(views, C_, dsm, xoff, yoff, res, zone, south, offsets, min_views=
             "sums": sums, "offsets": off}
 
 
+AGG_VOLUME = dict(shape=("H", "W", "Z"), side=(1, (1 << 31) - 1), cells=(1, (1 << 31) - 1))   # [H][W][Z] int32 of the aggregation entries
+
+
+def _agg_volume(name, t, what):
+    """quanta or sum: int32 [H][W][Z] with Z in [1, BN_SWEEP_MAX_LEVELS] and fewer than 2^31 elements -> H, W, Z."""
+    _need(name, t, what, I32, **AGG_VOLUME)
+    if t.shape[2] > L.BN_SWEEP_MAX_LEVELS:
+        raise ValueError(f"{name}: {what} {tuple(t.shape)} has more than {L.BN_SWEEP_MAX_LEVELS} levels")
+    return tuple(t.shape)
+
+
+def cost_quanta(cost, quantum, quanta=None, counters=None):
+    """A cost volume as integer quanta (bn_cost_quanta).  cost (Z, H, W) float32, NaN where a level is not valid at a cell; quantum > 0:
+    the cost of one quantum.  quanta (H, W, Z) int32 and counters (3,) int64 = (cells with a result, valid pairs, capped pairs) may be
+    given - the counters are accumulated into.  -> quanta, counters."""
+    name = "cost_quanta"
+    _need(name, cost, "cost", F32, ("Z", "H", "W"), side=(1, (1 << 31) - 1), cells=(1, (1 << 31) - 1))
+    Z, H, W = cost.shape
+    if Z > L.BN_SWEEP_MAX_LEVELS:
+        raise ValueError(f"{name}: cost {tuple(cost.shape)} has more than {L.BN_SWEEP_MAX_LEVELS} levels")
+    if isinstance(quantum, bool) or not isinstance(quantum, numbers.Real) or not (math.isfinite(quantum) and quantum > 0):
+        raise ValueError(f"{name}: quantum {quantum!r} must be finite and positive")
+    quanta = _out(name, quanta, "quanta", I32, (H, W, Z), cost.device, torch.empty)
+    counters = _out(name, counters, "counters", I64, (3,), cost.device, flat=True)
+    _on_device(name, cost, quanta, counters)
+    with torch.cuda.device(cost.device):
+        L.check(L.lib().bn_cost_quanta(_p(cost), Z, H, W, float(quantum), _p(quanta), _p(counters), _stream()), "bn_cost_quanta")
+    return quanta, counters
+
+
+def _agg_penalties(name, P1, P2):
+    """The penalties in quanta: integers (not bools) with 0 <= P1 <= P2 <= 2^20, or ValueError by name."""
+    for v in (P1, P2):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError(f"{name}: penalties P1={P1!r}, P2={P2!r} must be integers")
+    if not 0 <= P1 <= P2 <= L.BN_AGG_QINV:
+        raise ValueError(f"{name}: penalties P1={P1}, P2={P2} (0 <= P1 <= P2 <= {L.BN_AGG_QINV})")
+    return int(P1), int(P2)
+
+
+def cost_paths(quanta, P1, P2, mask=0xFF, sum=None):
+    """The minimum-cost paths of the directions in `mask` (bits 0 to 7, include/brdfnerf_hip.h) ADDED into sum (bn_cost_paths).
+    quanta (H, W, Z) int32 as cost_quanta gives them; P1 <= P2: the penalties in quanta; sum (H, W, Z) int32, zeroed when made here.
+    -> sum."""
+    name = "cost_paths"
+    H, W, Z = _agg_volume(name, quanta, "quanta")
+    P1, P2 = _agg_penalties(name, P1, P2)
+    if isinstance(mask, bool) or not isinstance(mask, numbers.Integral) or not 1 <= mask <= 0xFF:
+        raise ValueError(f"{name}: direction mask {mask!r} (bits 0 to 7, at least one)")
+    sum = _out(name, sum, "sum", I32, (H, W, Z), quanta.device)
+    _on_device(name, quanta, sum)
+    with torch.cuda.device(quanta.device):
+        L.check(L.lib().bn_cost_paths(_p(quanta), Z, H, W, P1, P2, int(mask), _p(sum), _stream()), "bn_cost_paths")
+    return sum
+
+
+def cost_pick(quanta, sum, level=None, sum_min=None, wins=None, sums=None):
+    """The first valid level of the smallest sum per cell (bn_cost_pick).  quanta, sum (H, W, Z) int32; level, sum_min (H, W) int32,
+    wins (Z,) int64 and sums (2,) int64 = (cells, the sum of sum_min) may be given - the counters are accumulated into.
+    -> {"level", "sum_min", "wins", "sums"}."""
+    name = "cost_pick"
+    H, W, Z = _agg_volume(name, quanta, "quanta")
+    _need(name, sum, "sum", I32, (H, W, Z))
+    dev = quanta.device
+    level = _out(name, level, "level", I32, (H, W), dev, torch.empty)
+    sum_min = _out(name, sum_min, "sum_min", I32, (H, W), dev, torch.empty)
+    wins = _out(name, wins, "wins", I64, (Z,), dev, flat=True)
+    sums = _out(name, sums, "sums", I64, (2,), dev, flat=True)
+    _on_device(name, quanta, sum, level, sum_min, wins, sums)
+    with torch.cuda.device(dev):
+        L.check(L.lib().bn_cost_pick(_p(quanta), _p(sum), Z, H, W, _p(level), _p(sum_min), _p(wins), _p(sums), _stream()), "bn_cost_pick")
+    return {"level": level, "sum_min": sum_min, "wins": wins, "sums": sums}
+
+
 def _cast_scalars(name, center, rng, xoff, yoff, res, zmax):
     center = tuple(float(v) for v in center)
     rng, xoff, yoff, res, zmax = float(rng), float(xoff), float(yoff), float(res), float(zmax)

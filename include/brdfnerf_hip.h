@@ -1286,6 +1286,43 @@ int bn_grid_sweep(const bn_mosaic_view *views_host, const bn_mosaic_view *views_
                   int32_t south, int32_t mode, const double *offsets_host, const double *offsets_dev, int32_t Z, int32_t min_views,
                   const double *colrow_in, int32_t *best_level, float *best_cost, uint8_t *best_count, float *altitude, float *cost,
                   unsigned long long *valid, unsigned long long *wins, unsigned long long *sums, void *stream);
+/* Semi-global aggregation of a cost volume (additive to ABI 7): bn_grid_sweep picks every cell's level on its own, and the variance of
+ * a few samples is a weak cue.  The three entries below turn the volume it returns into integer quanta, add over the grid the
+ * minimum-cost paths of up to 8 directions - a small penalty P1 for a change of one level between neighbouring cells, a larger P2 for
+ * a jump - and pick the level of the smallest sum: semi-global matching over the levels.  There is NO upstream counterpart.  Level
+ * adjacency is index adjacency: the levels are meant in ascending order of what they stand for.
+ *
+ * 1. quanta     bn_cost_quanta: cost float32 [Z][H][W], NaN where a level is not valid at a cell (bn_grid_sweep's `cost`), quantum > 0
+ *               in float64 -> quanta int32 [H][W][Z], the level fastest:
+ *               a cell with no non-NaN level: -1 at every level;  otherwise a NaN level: BN_AGG_QINV = 2^20;
+ *               a non-NaN level: t = (double)c / quantum (ONE float64 division) ; q = 2^20 - 1 if t >= 2^20 - 1, 0 if t <= 0, else
+ *               (int)rint(t), ties to even.  So +inf is the cap, and negatives, -0.0 and -inf are 0.
+ *               That division and rounding is the only floating-point arithmetic of the three entries.
+ *               counters uint64 [3] += (cells with a result, non-NaN (cell, level) pairs, pairs with t >= 2^20 - 1).
+ * 2. paths      bn_cost_paths: the directions r = (row step, column step) in bit order 0 to 7 of `mask`:
+ *               (0,+1) (0,-1) (+1,0) (-1,0) (+1,+1) (-1,-1) (+1,-1) (-1,+1).
+ *               c(p, d) = max(quanta[p][d], 0): a cell without a result is neutral - it passes messages on and restarts no path.
+ *               If p - r lies outside the grid: L_r(p, d) = c(p, d).  Otherwise, with m = min_k L_r(p - r, k):
+ *                 L_r(p, d) = c(p, d) + min(L_r(p - r, d), L_r(p - r, d - 1) + P1, L_r(p - r, d + 1) + P1, m + P2) - m
+ *               where the d - 1 term is absent at d = 0 and the d + 1 term at d = Z - 1.  All int32; 0 <= L_r - c <= P2.
+ *               sum int32 [H][W][Z]: sum[p][d] += L_r(p, d) for every direction of the mask - at most 8 x 2^21 over the 8 directions.
+ *               The entry ADDS: the CALLER zeroes sum, which is what lets launches and ranks split the directions.
+ * 3. pick       bn_cost_pick: level d of cell p is valid iff 0 <= quanta[p][d] < 2^20.
+ *               level int32 [H][W]: the valid level of the smallest sum[p][d], the FIRST of them on a tie (a strict <); -1 where no
+ *               level is valid.  sum_min int32 [H][W]: that sum; -1 where none.  (sum is taken as what step 2 leaves: >= 0.)
+ *               wins uint64 [Z] += the cells whose level is d ;  sums uint64 [2] += (cells with a level, the sum of their sum_min).
+ * counters, wins and sums are device memory, the CALLER zeroes them.  Everything after step 1 is integer: the sums are int32 atomics,
+ * every other output a plain store of its own cell.  No bit depends on the block order, on how the directions are split over
+ * launches, or on the number of ranks.
+ * Refused (BN_EINVAL, nothing launched, buffers untouched): a NULL pointer; Z outside [1, BN_SWEEP_MAX_LEVELS]; H or W < 1; H W Z >=
+ * 2^31; a quantum that is not finite or <= 0; P1 < 0, P2 < P1 or P2 > 2^20; a mask that is 0 or has bits above 0xFF. */
+#define BN_AGG_QINV 1048576
+int bn_cost_quanta(const float *cost, int32_t Z, int32_t H, int32_t W, double quantum, int32_t *quanta, unsigned long long *counters,
+                   void *stream);
+int bn_cost_paths(const int32_t *quanta, int32_t Z, int32_t H, int32_t W, int32_t P1, int32_t P2, int32_t mask, int32_t *sum,
+                  void *stream);
+int bn_cost_pick(const int32_t *quanta, const int32_t *sum, int32_t Z, int32_t H, int32_t W, int32_t *level, int32_t *sum_min,
+                 unsigned long long *wins, unsigned long long *sums, void *stream);
 /* Ray-level tail of a Lambertian step in ONE launch: bn_merged_composite_forward + bn_lambert_loss (shading, SNerfLoss,
  * DepthLoss; metrics.py:39-61,82-161) + bn_merged_composite_backward.  The prior arrays carry element strides.  ray_loss [R]
  * (nullable) and/or loss_acc (nullable): ray r's term is atomically added to loss_acc[r % loss_slots] - partial sums the
